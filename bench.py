@@ -27,8 +27,14 @@ instead).  Weak scaling (`weak`, N > 1, secondary): 4096 workers PER GPU, 4096 x
 graph construction.
 
 Prints ONE JSON line on rank 0 (driver contract), with `roofline` for the fused
-round kernel (HIP-event timed, same timed region) and `cpu_baseline` (the oracle,
-i.e. the reference's per-worker numpy round, on a bounded sample, rank 0, N=1 only).
+round kernel (HIP-event timed, same timed region).
+
+A plain run does what `value` needs and no more: set-up, warmup, the `--steps` timed rounds, the
+line.  `--full` adds every other measurement after the headline leg: the secondary legs at N=1
+above, `cpu_baseline` (the oracle, i.e. the reference's per-worker numpy round, on a bounded
+sample, rank 0, N=1 only), and at N > 1 the headline leg with the exchange in its other forms,
+the weak leg and the transport probe.  `--dump-outputs DIR` writes what the timed rounds returned
+(objective.npy, consensus.npy) and the iterates they left (models.npy) for comparing two builds.
 """
 import argparse
 import json
@@ -579,6 +585,26 @@ def run_leg(S, args, world, barrier, dev):
     return dt, launches, kr_ms, every, obj, cons
 
 
+DUMP_BYTES = 48 << 20  # of iterates over all ranks (the whole dump stays under 64 MB)
+
+
+def dump_outputs(path, eng, obj, cons, world, rank):
+    """--dump-outputs: what a caller of the timed rounds holds after the last one -- the objective and
+    consensus entries they returned (rank 0) and this rank's iterates, float64.  Iterates beyond this rank's
+    share of DUMP_BYTES are cut to a fixed sample of worker rows (seeded: the same rows in every run)."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    x = eng.get_models()
+    keep = max(1, (DUMP_BYTES // world) // (x.shape[1] * 8))
+    if keep < x.shape[0]:
+        x = x[np.sort(np.random.default_rng(0).choice(x.shape[0], size=keep, replace=False))]
+    np.save(os.path.join(path, "models.npy" if world == 1 else f"models_rank{rank}.npy"), x)
+    if rank == 0:
+        np.save(os.path.join(path, "objective.npy"), np.asarray(obj, dtype=np.float64))
+        np.save(os.path.join(path, "consensus.npy"), np.asarray(cons, dtype=np.float64))
+
+
 def per_rank(world, item):
     """item of every rank (rank order), gathered on every rank (host objects)."""
     import torch.distributed as dist
@@ -711,6 +737,14 @@ def main():
     ap.add_argument("--steps", type=int, default=300,
                     help="rounds timed (one run: the last round's metrics pass is amortised over them)")
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline leg, every other measurement too: at N=1 the f(x*) solver, the drop-in "
+                         "trainer legs, the f64-storage / f32 legs and the CPU baseline; at N > 1 the other exchange "
+                         "forms, the weak leg and the transport probe (each still skipped by its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed rounds, write the objective and consensus entries they returned and the "
+                         "iterates they left as DIR/<name>.npy (float64; iterates past 48 MB: a fixed seeded sample "
+                         "of worker rows)")
     ap.add_argument("--workers", type=int, default=4096, help="workers per GPU (C3 weak-scaling leg)")
     ap.add_argument("--strong-workers", type=int, default=4096,
                     help="C3 strong scaling (the headline): workers in total over the N GPUs (the metric's N = 4096)")
@@ -729,12 +763,12 @@ def main():
     ap.add_argument("--degree", type=int, default=4)
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
     ap.add_argument("--cpu-procs", type=int, default=0, help="CPU baseline processes (0: the box's CPU share)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full, N=1: skip the CPU baseline")
     ap.add_argument("--no-alt-exchange", action="store_true",
-                    help="N > 1: skip the headline leg's timings with the exchange in the other stream form and "
-                         "over the other transport")
+                    help="--full, N > 1: skip the headline leg's timings with the exchange in the other stream form "
+                         "and over the other transport")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="N=1: skip the f64-storage / f32 legs, the f(x*) solver and the drop-in trainer leg")
+                    help="--full, N=1: skip the f64-storage / f32 legs, the f(x*) solver and the drop-in trainer leg")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend for N > 1 (gloo: 1-GPU rehearsal)")
     ap.add_argument("--timeout", type=float, default=None,
                     help="seconds any collective may take before the job fails (default DOPT_PG_TIMEOUT or 300)")
@@ -819,6 +853,8 @@ def main():
     n = plan.n_local
     setup_s = time.time() - T_START  # launch, process group, graph + partition, shard generation, plan
     dt, launches, kr_ms, every, obj, cons = run_leg(S, args, world, barrier, dev)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, eng, obj, cons, world, rank)
 
     esz = 4 if eng.dtype == _dopt.F32 else 8
     xesz = 4 if eng.data_dtype == _dopt.F32 else 8
@@ -886,8 +922,9 @@ def main():
                                            "send_bytes_out_per_round": (S.comm or {}).get("send_bytes_out_per_round")})
     if args.config != "c3":
         out["metric"] = f"worker-iters/sec ({args.config.upper()}, secondary config)"
-    secondary = rank == 0 and world == 1 and not args.phase and args.config == "c3" and not args.no_secondary
-    if world > 1 and args.config == "c3" and S.flush is not None and not args.no_alt_exchange:
+    secondary = (args.full and rank == 0 and world == 1 and not args.phase and args.config == "c3"
+                 and not args.no_secondary)
+    if args.full and world > 1 and args.config == "c3" and S.flush is not None and not args.no_alt_exchange:
         side = "0" if S.comm.get("exchange_beside_gradient") else "1"
         legs = [("alt_exchange", {"DOPT_LAGGED_SIDE": side},
                  "the exchange on the side stream beside the gradient kernel (DOPT_LAGGED_SIDE=1)" if side == "1"
@@ -923,14 +960,14 @@ def main():
     if args.pcie and world == 1 and args.config == "c3":
         out["pcie"] = pcie_leg(eng, top, n, d, m, b, lam, eta0, args.steps, dt)
     eng.close()
-    if args.config == "c3" and world > 1 and args.scaling == "both":
+    if args.full and args.config == "c3" and world > 1 and args.scaling == "both":
         log(f"weak-scaling leg: {args.workers} workers per rank, {args.workers * world} over {world} ranks")
         try:  # secondary: a failure here must not cost the line its value (every rank raises alike)
             out["weak"] = extra_leg(args, world, rank, dev, barrier, "weak")
         except Exception as e:  # noqa: BLE001
             log(f"weak leg failed: {e!r}")
             out["weak"] = {"error": repr(e)[:300]}
-    if world > 1 and getattr(S, "exchange_shape", None) is not None:
+    if args.full and world > 1 and getattr(S, "exchange_shape", None) is not None:
         log("transport probe: the headline leg's exchange and an 8 MiB all-reduce alone")
         try:  # diagnostic only, as above
             out["transport_probe"] = transport_probe(args, world, dev, barrier, S.exchange_shape)
@@ -948,7 +985,7 @@ def main():
             legs["f32"] = secondary_leg(dev, "float32", None, top, n, d, m, args.steps, args.warmup, lam, eta0,
                                         barrier, args.event_every)
         out["legs"] = legs
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.config == "c3":
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and args.config == "c3":
         log("cpu baseline")
         out["cpu_baseline"] = cpu_baseline(args.cpu_seconds, args.cpu_procs or None)
     out["setup_s"] = setup_s  # rank 0: process start -> the headline leg's warmup

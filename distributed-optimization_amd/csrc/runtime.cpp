@@ -31,6 +31,7 @@
 
 #include <algorithm>
 #include <chrono>
+#include <mutex>
 #include <thread>
 #include <string>
 #include <vector>
@@ -218,6 +219,7 @@ struct dopt_ctx {
   char* ipc_send = nullptr;             // [2 x ipc_slot bytes]
   int64_t ipc_slot = 0;
   hipEvent_t ipc_ev = nullptr;          // interprocess: recorded behind each slot's rows and sums
+  bool ipc_ev_shared = false;           // its handle was exported (else ipc_publish counts finished records)
   std::vector<void*> ipc_open;          // the peers' allocations opened here
   std::vector<hipEvent_t> ipc_pev;      // the peers' events, opened here
   std::vector<int32_t> ipc_peers;       // ranks pulled from (not this one)
@@ -324,10 +326,40 @@ int dalloc(void** p, size_t bytes) {
 int ipc_publish(dopt_ctx* c);
 int ipc_pull(dopt_ctx* c);
 
+// The pull transport's send slots are uncached device memory, and the HIP runtime of some hosts faults when
+// uncached memory that a kernel has read is freed: a context's slots go back to this list instead (after the
+// device has drained), and the next export of that device and size takes them from it.
+struct UcBlock {
+  int device;
+  size_t bytes;
+  char* p;
+};
+std::mutex g_uc_mu;
+std::vector<UcBlock> g_uc_free;
+
+void uc_give(int device, size_t bytes, char* p) {
+  std::lock_guard<std::mutex> g(g_uc_mu);
+  g_uc_free.push_back(UcBlock{device, bytes, p});
+}
+
+hipError_t uc_take(int device, size_t bytes, char** p) {
+  {
+    std::lock_guard<std::mutex> g(g_uc_mu);
+    for (size_t i = 0; i < g_uc_free.size(); ++i)
+      if (g_uc_free[i].device == device && g_uc_free[i].bytes == bytes) {
+        *p = g_uc_free[i].p;
+        g_uc_free.erase(g_uc_free.begin() + (long)i);
+        return hipSuccess;
+      }
+  }
+  return hipExtMallocWithFlags((void**)p, bytes, hipDeviceMallocUncached);
+}
+
 // The pull transport's peer side: handles opened by dopt_lagged_ipc_import closed, its arrays freed.
 void ipc_close(dopt_ctx* c) {
-  // (no pull of this context may still read a peer's allocation when its mapping goes: teardown and setup only)
-  if (!c->ipc_open.empty()) (void)hipDeviceSynchronize();
+  // (no pull of this context may still read a peer's allocation when its mapping goes, and no publishing host
+  // function may still write the caller's counters: teardown and setup only)
+  if (!c->ipc_open.empty() || (c->ipc && !c->ipc_ev_shared)) (void)hipDeviceSynchronize();
   for (void* q : c->ipc_open)
     if (q) (void)hipIpcCloseMemHandle(q);
   for (hipEvent_t e : c->ipc_pev)
@@ -1331,7 +1363,7 @@ int dopt_destroy(dopt_ctx* c) {
   dfree_t(c->lg_sum_in);
   dfree_t(c->lg_sum_out);
   ipc_close(c);
-  if (c->ipc_send) (void)hipFree(c->ipc_send);
+  if (c->ipc_send) uc_give(c->device, (size_t)(2 * c->ipc_slot), c->ipc_send);
   if (c->ipc_ev) (void)hipEventDestroy(c->ipc_ev);
   for (hipEvent_t e : c->ev) (void)hipEventDestroy(e);
   if (c->lg_side_ev) (void)hipEventDestroy(c->lg_side_ev);
@@ -2690,12 +2722,39 @@ int lagged_mark_exchange(dopt_ctx* c) {
 // again for record r + 2, in a mix that waited for its own pulls of record r + 1, which waited for every
 // peer's event r + 1 -- recorded after that peer's mix that followed its pulls of record r.  The host wait is
 // bounded (timeout_s, the job's collective bound).
+// A rank whose runtime cannot export its event publishes record r from a host function on the stream instead,
+// i.e. once the record is written; the same argument holds with "finished" for "recorded".
 namespace {
+struct IpcRecord {
+  int64_t* cnt;
+  int64_t rec;
+};
+
+void ipc_record_done(void* q) {
+  IpcRecord* r = (IpcRecord*)q;
+  __atomic_store_n(r->cnt, r->rec, __ATOMIC_RELEASE);
+  delete r;
+}
+
 int ipc_publish(dopt_ctx* c) {
   if (!c->ipc) return DOPT_OK;
-  HIPOK(hipEventRecord(c->ipc_ev, c->lg_side ? c->lg_side : c->stream));
+  hipStream_t s = c->lg_side ? c->lg_side : c->stream;
+  if (c->ipc_ev_shared) {
+    HIPOK(hipEventRecord(c->ipc_ev, s));
+    c->ipc_rec += 1;
+    __atomic_store_n(c->ipc_cnt + c->lg_rank, c->ipc_rec, __ATOMIC_RELEASE);
+    return DOPT_OK;
+  }
+  // no exported event (dopt_lagged_ipc_export): the count is published by the stream itself, once the rows and
+  // sums of this record are written, and the peers' pulls -- launched after they have seen it -- wait for no event
+  IpcRecord* r = new IpcRecord{c->ipc_cnt + c->lg_rank, c->ipc_rec + 1};
+  hipError_t e = hipLaunchHostFunc(s, ipc_record_done, r);
+  if (e != hipSuccess) {
+    delete r;
+    return fail(DOPT_ERR_HIP, "hipLaunchHostFunc (publishing record %lld): %s", (long long)(c->ipc_rec + 1),
+                hipGetErrorString(e));
+  }
   c->ipc_rec += 1;
-  __atomic_store_n(c->ipc_cnt + c->lg_rank, c->ipc_rec, __ATOMIC_RELEASE);
   return DOPT_OK;
 }
 
@@ -2777,17 +2836,25 @@ int dopt_lagged_ipc_export(dopt_ctx* c, uint8_t* mem_handle, uint8_t* event_hand
   const int64_t slot = (std::max<int64_t>(1, c->n_send) * row + 255) / 256 * 256;
   if (c->ipc_send) {
     HIPOK(hipDeviceSynchronize());  // (a previous chain's pulls by peers finished with their runner)
-    HIPOK(hipFree(c->ipc_send));
+    uc_give(c->device, (size_t)(2 * c->ipc_slot), c->ipc_send);
     c->ipc_send = nullptr;
   }
   // uncached: the mix kernels' writes of the send rows go through to memory, where a peer's pull (on another
   // GPU: over xGMI) reads them after the interprocess event, with no dirty line left in this GPU's L2
-  HIPOK(hipExtMallocWithFlags((void**)&c->ipc_send, (size_t)(2 * slot), hipDeviceMallocUncached));
+  HIPOK(uc_take(c->device, (size_t)(2 * slot), &c->ipc_send));
+  c->ipc_slot = slot;
   HIPOK(hipMemset(c->ipc_send, 0, (size_t)(2 * slot)));
   if (!c->ipc_ev) HIPOK(hipEventCreateWithFlags(&c->ipc_ev, hipEventInterprocess | hipEventDisableTiming));
   HIPOK(hipIpcGetMemHandle((hipIpcMemHandle_t*)mem_handle, c->ipc_send));
-  HIPOK(hipIpcGetEventHandle((hipIpcEventHandle_t*)event_handle, c->ipc_ev));
-  c->ipc_slot = slot;
+  // The runtime registers host memory to export an event, which some hosts refuse.  There the event's handle
+  // stays all zero: this rank publishes its records as the stream finishes them (ipc_publish) and its peers
+  // open no event of its.
+  memset(event_handle, 0, DOPT_IPC_HANDLE_BYTES);
+  c->ipc_ev_shared = hipIpcGetEventHandle((hipIpcEventHandle_t*)event_handle, c->ipc_ev) == hipSuccess;
+  if (!c->ipc_ev_shared) {
+    memset(event_handle, 0, DOPT_IPC_HANDLE_BYTES);
+    (void)hipGetLastError();  // (the refusal is not the next launch's error)
+  }
   *slot_bytes = slot;
   return DOPT_OK;
 }
@@ -2827,13 +2894,16 @@ int dopt_lagged_ipc_import(dopt_ctx* c, int32_t world, int32_t rank, const uint8
         return fail(DOPT_ERR_HIP, "rank %d: hipIpcOpenMemHandle of peer %d: %s", rank, p, hipGetErrorString(e));
       }
       c->ipc_open.push_back(q);
-      hipEvent_t ev = nullptr;
-      e = hipIpcOpenEventHandle(&ev, *(const hipIpcEventHandle_t*)(event_handles + (size_t)p * DOPT_IPC_HANDLE_BYTES));
-      if (e != hipSuccess) {
-        ipc_close(c);
-        return fail(DOPT_ERR_HIP, "rank %d: hipIpcOpenEventHandle of peer %d: %s", rank, p, hipGetErrorString(e));
-      }
-      c->ipc_pev.push_back(ev);
+      const uint8_t* eh = event_handles + (size_t)p * DOPT_IPC_HANDLE_BYTES;
+      if (std::any_of(eh, eh + DOPT_IPC_HANDLE_BYTES, [](uint8_t v) { return v != 0; })) {
+        hipEvent_t ev = nullptr;
+        e = hipIpcOpenEventHandle(&ev, *(const hipIpcEventHandle_t*)eh);
+        if (e != hipSuccess) {
+          ipc_close(c);
+          return fail(DOPT_ERR_HIP, "rank %d: hipIpcOpenEventHandle of peer %d: %s", rank, p, hipGetErrorString(e));
+        }
+        c->ipc_pev.push_back(ev);
+      }  // (else p publishes finished records: dopt_lagged_ipc_export)
       c->ipc_peers.push_back(p);
       base = (const char*)q;
     }

@@ -461,7 +461,10 @@ int dopt_lagged_exchange(dopt_ctx *ctx);
  * dopt_lagged_transport, the neighbour reads of the reference's mix (trainer.py:173) across ranks.
  * dopt_lagged_ipc_export: after dopt_set_halo -- the context keeps its send rows in two slots (round
  *   parity) of an allocation of its own instead of the caller's send buffer; returns that allocation's IPC
- *   handle, an interprocess event's handle (DOPT_IPC_HANDLE_BYTES each) and the bytes of one slot.
+ *   handle, an interprocess event's handle (DOPT_IPC_HANDLE_BYTES each) and the bytes of one slot.  Where the
+ *   runtime cannot export an event (it registers host memory for one, which some hosts refuse), the event's
+ *   handle is all zero: that rank then counts a record in `counters` when its stream has written it, not when
+ *   the event is recorded, and its peers pull after the count alone.
  * dopt_lagged_ipc_import: after every rank exported and dopt_lagged_exchange_layout: per rank p (rank order,
  *   world entries of each array), p's two handles and slot bytes, the byte offset in p's slot of the block
  *   p sends to this rank and recv_rows[p] rows that block holds (this rank's own entry: its self block,

@@ -17,7 +17,7 @@ for s in $STEPS; do
   case $s in
     smoke) step smoke 300 python -u -c "import __graft_entry__ as g; g.smoke()" ;;
     tests) step tests 900 python -u -m pytest tests -m gpu -x -v --timeout 300 --timeout-method thread ${PYTEST_ARGS:-} ;;
-    bench) step bench 600 python -u bench.py ${BENCH_ARGS:-} ;;
+    bench) step bench 600 python -u bench.py --full ${BENCH_ARGS:-} ;;
     dist2) step dist2 300 python -u -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 2 --backend gloo --workers 1024 --steps 5 --warmup 1 ;;
     probe) step probe 120 ./tools/bw_probe ;;
     variants) step variants 600 python -u tools/kr_variants.py ;;

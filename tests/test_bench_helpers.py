@@ -47,6 +47,29 @@ def test_bytes_and_committed_traffic(config, kernel, dt, xdt, n, d, m, gb, prof)
     assert 1.0 <= traffic / b < 1.02, traffic / b
 
 
+def test_dump_outputs_writes_float64_arrays_and_a_fixed_sample(tmp_path, monkeypatch):
+    """--dump-outputs: the timed rounds' metrics and the iterates as float64 .npy; iterates past the byte
+    budget are cut to the same sorted worker rows in every run."""
+    import numpy as np
+
+    x = np.arange(40 * 8, dtype=np.float64).reshape(40, 8)
+    eng = types.SimpleNamespace(get_models=lambda: x.copy())
+    obj, cons = np.linspace(1.0, 0.5, 6), np.linspace(0.0, 0.1, 6)
+    bench.dump_outputs(str(tmp_path / "a"), eng, obj, cons, 1, 0)
+    assert sorted(os.listdir(tmp_path / "a")) == ["consensus.npy", "models.npy", "objective.npy"]
+    got = {n: np.load(tmp_path / "a" / f"{n}.npy") for n in ("models", "objective", "consensus")}
+    assert all(a.dtype == np.float64 for a in got.values())
+    assert np.array_equal(got["models"], x) and np.array_equal(got["objective"], obj)
+    assert np.array_equal(got["consensus"], cons)
+    monkeypatch.setattr(bench, "DUMP_BYTES", 10 * 8 * 8)  # room for 10 of the 40 rows
+    for k in "bc":
+        bench.dump_outputs(str(tmp_path / k), eng, obj, cons, 1, 0)
+    b, c = np.load(tmp_path / "b" / "models.npy"), np.load(tmp_path / "c" / "models.npy")
+    assert b.shape == (10, 8) and np.array_equal(b, c)
+    rows = (b[:, 0] / 8).astype(int)
+    assert np.all(np.diff(rows) > 0) and np.array_equal(b, x[rows])
+
+
 def test_traffic_lookup_is_per_configuration():
     """C3 and C4 launch the same kernel instance: each line reads its own configuration's file."""
     t3, s3, _ = bench.pmc_traffic(C3, "c3")
