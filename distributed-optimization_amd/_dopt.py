@@ -64,6 +64,9 @@ _SIGS = {
     "dopt_run_dsgd": ([_P, _I64, _I64, _D, _I64, _P, _D, _D, _D, ctypes.c_uint32, _P, _P, _P], ctypes.c_int),
     "dopt_run_dsgd_pipelined": ([_P, _I64, _I64, _D, _I64, _P, _D, _D, _D, ctypes.c_uint32, _P, _P, _P, _P],
                                 ctypes.c_int),
+    "dopt_run_gt": ([_P, _I64, _I64, _D, _I64, _P, _D, _D, _D, ctypes.c_uint32, _P, _P, _P], ctypes.c_int),
+    "dopt_gt_set_state": ([_P, _P, _P], ctypes.c_int),
+    "dopt_gt_get_state": ([_P, _P, _P], ctypes.c_int),
     "dopt_run_centralized": ([_P, _I64, _I64, _D, _I64, _P, _D, _D, _D, ctypes.c_uint32, _P, _P], ctypes.c_int),
     "dopt_eval_gradient": ([_P, ctypes.c_int, _I64, _I64, _P, _P, _P, _D, _P], ctypes.c_int),
     "dopt_eval_objective": ([_P, ctypes.c_int, _I64, _I64, _P, _P, _P, _D, _P], ctypes.c_int),
@@ -434,6 +437,33 @@ class Engine:
         k = n.value
         res = (None if obj is None else obj[:k]), (None if cons is None else cons[:k])
         return res + (tim,) if want_time else res
+
+    def run_gt(self, T, eta0, batch, lam_grad, lam_obj, f_opt=0.0, idx=None, t0=0,
+               objective=True, consensus=True, want_time=True):
+        """dopt_run_gt: T rounds of gradient tracking from the tracker state on the context;
+        arguments and return value as run_dsgd."""
+        T = int(T)
+        obj = np.zeros(T) if objective else None
+        cons = np.zeros(T) if consensus else None
+        tim = np.zeros(T) if want_time else None
+        if idx is not None:
+            idx = np.ascontiguousarray(idx, dtype=np.int32)
+        flags = (RUN_OBJECTIVE if objective else 0) | (RUN_CONSENSUS if consensus else 0)
+        check(lib().dopt_run_gt(self._h, int(t0), T, float(eta0), int(batch), _ptr(idx), float(lam_grad),
+                                float(lam_obj), float(f_opt), flags, _ptr(obj), _ptr(cons), _ptr(tim)))
+        return obj, cons, tim
+
+    def gt_set_state(self, y=None, g=None):
+        """Trackers y and last stochastic gradients g (N x d each); None = zeros."""
+        y = None if y is None else np.ascontiguousarray(y, dtype=np.float64).reshape(self.n, self.d)
+        g = None if g is None else np.ascontiguousarray(g, dtype=np.float64).reshape(self.n, self.d)
+        check(lib().dopt_gt_set_state(self._h, _ptr(y), _ptr(g)))
+
+    def gt_get_state(self):
+        y = np.empty((self.n, self.d), dtype=np.float64)
+        g = np.empty((self.n, self.d), dtype=np.float64)
+        check(lib().dopt_gt_get_state(self._h, _ptr(y), _ptr(g)))
+        return y, g
 
     def run_centralized(self, T, eta0, batch, lam_grad, lam_obj, f_opt=0.0, idx=None, t0=0,
                         objective=True, want_time=True):

@@ -239,6 +239,23 @@ hipError_t launch_round_f64(int problem, int cpl, bool grad, bool met, const Rou
 hipError_t launch_round_x32(int problem, int cpl, bool grad, bool met, const RoundArgs& a, int n_groups,
                             hipStream_t s);
 
+// ---- gradient tracking (k_round_gt.inc): one launch per round, one workgroup per worker
+//   y_new_i = sum_j W_ij y_j + g_new_i - g_i,   x_new_i = sum_j W_ij x_j - eta y_new_i,   g_i <- g_new_i
+// r: the D-SGD round's arguments (x_old / x_new, idx, the CSR matrix, eta, lam, xbar and the slabs);
+// r.flags: F_STEP (without it the launch only takes the metrics of x_old at xbar), F_CONS, and --
+// full-shard batches only -- F_LOSS.  No halo rows, no F_MEAN.
+struct GtArgs {
+  RoundArgs r;
+  const void* y_old;  // [n x ld] T trackers before the round (read only during the round)
+  void* y_new;        // [n x ld] T trackers after the round
+  void* g_prev;       // [n x ld] T the previous stochastic gradients, replaced in place
+  int32_t epi_mix;    // A/B: both mixes in the epilogue through L2 instead of the prologue + LDS (same bits)
+};
+// per element-type pair (gt_f32.hip / gt_f64.hip / gt_x32.hip); cpl = 16-byte DATA chunks per lane
+hipError_t launch_gt_f32(int problem, int cpl, bool met, const GtArgs& a, int n_workers, hipStream_t s);
+hipError_t launch_gt_f64(int problem, int cpl, bool met, const GtArgs& a, int n_workers, hipStream_t s);
+hipError_t launch_gt_x32(int problem, int cpl, bool met, const GtArgs& a, int n_workers, hipStream_t s);
+
 // ---- large d (column-blocked): one workgroup per (worker, group of 64-chunk column blocks)
 constexpr int kSplitMaxRows = 64;  // rows held in registers by a step workgroup (16 per wave)
 // Step: g_i = (1/nb) sum_k coef_k x_k + lam x_i, x_i' = mix - eta g_i (block by block); with

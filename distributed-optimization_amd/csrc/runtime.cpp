@@ -12,6 +12,7 @@
 //   slabs  [N]        f64   per-worker consensus / objective partials
 //   rp/ci/cw                CSR mixing matrix (diagonal included), cw in T
 //   G      [N x ld]     T   per-worker gradients (centralized trainer, multi-GPU phases)
+//   ys[2], gprev [N x ld] T   gradient tracking: tracker ping-pong, previous stochastic gradients
 //
 // Launch schedule of one D-SGD round t (metrics every round):
 //   k_round(t)       grad + mix + step for every worker, and the consensus /
@@ -20,6 +21,7 @@
 //   k_colsum_part(t) + k_colsum_final(t)   xbar_{t+1}; one extra block folds history[t-1]
 // plus one metrics-only pass after the last round.  Only a separate objective dataset
 // (X_full that is not the shards) takes a metrics-only pass every round.
+// A gradient-tracking round (dopt_run_gt) has the same schedule with k_round_gt in k_round's place.
 // The multi-GPU phase functions (dopt_phase_*) split the same round at its
 // communication points; distributed.py drives them.
 #include <hip/hip_runtime.h>
@@ -139,6 +141,11 @@ struct dopt_ctx {
   void* xg[2] = {nullptr, nullptr};
   int gcur = 0;
   void* G = nullptr;
+  // gradient tracking (dopt_run_gt): tracker ping-pong and the previous stochastic gradients,
+  // [N x ld] T each, allocated (zero) by the first call that needs them
+  void* ys[2] = {nullptr, nullptr};
+  int ycur = 0;
+  void* gprev = nullptr;
   void* xbar[2] = {nullptr, nullptr};
   int xb = 0;  // xbar[xb] = average of the current iterates
   double* S = nullptr;             // [ld] column sums of the current iterates (complete-graph mixing)
@@ -474,6 +481,10 @@ int alloc_state(dopt_ctx* c) {
     HIPOK(hipMemsetAsync(c->xbar[k], 0, c->ld * c->esz, c->stream));
   }
   dfree(c->G);  // allocated on first centralized run
+  dfree(c->ys[0]);  // new data: the tracker state of dopt_run_gt is gone
+  dfree(c->ys[1]);
+  dfree(c->gprev);
+  c->ycur = 0;
   c->cur = 0;
   c->gcur = 0;
   c->xb = 0;
@@ -1329,8 +1340,8 @@ int dopt_destroy(dopt_ctx* c) {
   (void)hipSetDevice(c->device);
   if (c->stream) (void)hipStreamSynchronize(c->stream);
   if (c->own_stream) (void)hipStreamSynchronize(c->own_stream);
-  for (void** p : {&c->X, &c->y, &c->Xo, &c->yo, &c->xs[0], &c->xs[1], &c->xg[0], &c->xg[1], &c->G,
-                   &c->xbar[0], &c->xbar[1], &c->cw, &c->staging, &c->sx, &c->wdiag, &c->coef})
+  for (void** p : {&c->X, &c->y, &c->Xo, &c->yo, &c->xs[0], &c->xs[1], &c->xg[0], &c->xg[1], &c->G, &c->ys[0], &c->ys[1],
+                   &c->gprev, &c->xbar[0], &c->xbar[1], &c->cw, &c->staging, &c->sx, &c->wdiag, &c->coef})
     dfree(*p);
   dfree_t(c->off);
   dfree_t(c->offo);
@@ -1821,6 +1832,175 @@ int dopt_run_centralized(dopt_ctx* c, int64_t t0, int64_t T, double eta0, int64_
     if ((rc = history(c, T - 1, c->xg[c->gcur], false, true, c->n))) return rc;
   }
   return finish_run(c, T, T, lam_obj, f_opt, want_obj ? obj_out : nullptr, nullptr, time_out);
+}
+
+// ---------------------------------------------------------------------------- gradient tracking
+namespace {
+
+// Tracker state of dopt_run_gt: y = 0, g = 0 until a run or dopt_gt_set_state says otherwise.
+int ensure_gt(dopt_ctx* c) {
+  if (c->ys[0] && c->ys[1] && c->gprev) return DOPT_OK;
+  const size_t st = (size_t)std::max<int64_t>(1, c->n) * c->ld * c->esz;
+  int rc;
+  for (void** p : {&c->ys[0], &c->ys[1], &c->gprev}) {
+    if ((rc = dalloc(p, st))) return rc;
+    HIPOK(hipMemsetAsync(*p, 0, st, c->stream));
+  }
+  c->ycur = 0;
+  return DOPT_OK;
+}
+
+hipError_t launch_gt(dopt_ctx* c, bool met, const GtArgs& g) {
+  if (c->dtype == DOPT_F32) return launch_gt_f32(c->problem, c->cpl, met, g, (int)c->n, c->stream);
+  if (c->xdtype == DOPT_F32) return launch_gt_x32(c->problem, c->cpl, met, g, (int)c->n, c->stream);
+  return launch_gt_f64(c->problem, c->cpl, met, g, (int)c->n, c->stream);
+}
+
+int check_gt(dopt_ctx* c) {
+  if (!c->have_data) return fail(DOPT_ERR_STATE, "no shards loaded");
+  if (c->split)
+    return fail(DOPT_ERR_UNSUPPORTED, "gradient tracking: rows of %lld elements are column-blocked; the tracking "
+                "round holds a row per wave (at most %d 16-byte chunks per lane)", (long long)c->d,
+                max_chunks_per_lane(c->dtype, c->xdtype));
+  return DOPT_OK;
+}
+
+// T rounds of gradient tracking, modelled on run_dsgd's row-resident branch: k_round_gt, then the
+// column sums of the new iterates with the history row of the previous round folded in.  Round h's
+// launch takes the metrics of x_h at xbar_h (history[h - 1]) in its pass; the row of the last
+// iterates takes one more launch of the same kernel without the step, folded by the same
+// column-sum launch as every other row -- so a run split into several calls computes every history
+// entry with the same code in the same order.  Host minibatches (idx) and a separate objective
+// dataset: the kernel fuses the consensus only and the objective takes the metrics-only pass after
+// every round, as D-SGD's unfused rounds do.
+int run_gt(dopt_ctx* c, int64_t t0, int64_t T, double eta0, int64_t batch, const int32_t* idx, double lam_grad,
+           double lam_obj, double f_opt, uint32_t flags, double* obj_out, double* cons_out, double* time_out) {
+  CHECK_ARG(c, "ctx is NULL");
+  int rc;
+  if ((rc = check_gt(c))) return rc;
+  if (!c->have_topo) return fail(DOPT_ERR_STATE, "no topology set");
+  if (c->mean_mix)
+    return fail(DOPT_ERR_UNSUPPORTED, "gradient tracking: mean mixing (dopt_set_mixing_mean) is not supported; give "
+                "the complete graph as CSR (dopt_set_topology)");
+  if (c->n_halo > 0 || c->n_send > 0 || c->sptr)
+    return fail(DOPT_ERR_UNSUPPORTED, "gradient tracking: contexts with a halo plan (multi-GPU slices) are not "
+                "supported");
+  if (!idx && batch < c->max_m && c->sampler == DOPT_SAMPLE_DEVICE)
+    return fail(DOPT_ERR_UNSUPPORTED, "gradient tracking: the device sampler is not supported; pass idx");
+  if ((rc = check_run(c, T, batch, idx, true))) return rc;
+  if ((rc = set_device(c))) return rc;
+  if ((rc = rs_end(c))) return rc;
+  c->carry_pending = false;
+  c->send_fresh = false;
+  if (T == 0) return DOPT_OK;
+  if ((rc = ensure_hist(c, T + 1))) return rc;
+  if ((rc = ensure_gt(c))) return rc;
+  const bool want_obj = flags & DOPT_RUN_OBJECTIVE, want_cons = flags & DOPT_RUN_CONSENSUS;
+  const bool metrics = want_obj || want_cons;
+  const bool fuse_loss = want_obj && !idx && !c->obj_sep;  // the pass walks every objective row
+  const bool pass_loss = want_obj && !fuse_loss;
+  const char* epi_env = getenv("DOPT_GT_EPIMIX");  // A/B knob, read per call: 1 = both mixes in the epilogue (same bits)
+  const bool epi = epi_env && atoi(epi_env) != 0;
+  const int64_t CH = idx ? idx_chunk_rounds(c, T, batch) : 1;
+  int& xb = c->xb;
+  if ((rc = colsum_current(c))) return rc;  // xbar of the starting iterates
+  HIPOK(launch_stamp(c->stamps, c->stream));
+
+  auto gt_args = [&](bool step, bool met) {
+    GtArgs g;
+    memset(&g, 0, sizeof(g));
+    g.r = base_args(c);
+    g.r.x_old = c->xs[c->cur];
+    g.r.x_new = c->xs[c->cur ^ 1];
+    g.r.xbar = c->xbar[xb];
+    g.r.lam = lam_grad;
+    g.r.b = batch;
+    g.r.flags |= (step ? F_STEP : 0) | (met && want_cons ? F_CONS : 0) | (met && fuse_loss ? F_LOSS : 0);
+    g.y_old = c->ys[c->ycur];
+    g.y_new = c->ys[c->ycur ^ 1];
+    g.g_prev = c->gprev;
+    g.epi_mix = epi ? 1 : 0;
+    if (g.r.flags & F_LOSS) c->loss_groups = c->n;  // per-worker loss slabs
+    return g;
+  };
+  // history row `row` = the slabs of the current launch (and, pass_loss, of the last metrics pass) at xbar[xb]
+  auto fold_args = [&](int64_t row) {
+    double* hr = c->hraw + 3 * row;
+    return FoldArgs{want_cons ? c->slab_cons : nullptr, c->n, want_obj ? c->slab_loss : nullptr, c->loss_groups,
+                    want_obj ? c->xbar[xb] : nullptr, hr, hr + 1, hr + 2};
+  };
+
+  for (int64_t h = 0; h < T; ++h) {
+    const int64_t t = t0 + h;
+    if (idx && h % CH == 0) {
+      if ((rc = upload_idx_chunk(c, idx, h, std::min(CH, T - h), batch))) return rc;
+    }
+    const bool met = metrics && h > 0;
+    GtArgs g = gt_args(true, met);
+    g.r.idx = idx ? c->idx + (h % CH) * c->n * batch : nullptr;
+    g.r.eta = eta0 / sqrt((double)(t + 1));  // trainer.py:138-140
+    if (c->prof && (rc = prof_event(c, false))) return rc;
+    HIPOK(launch_gt(c, metrics, g));
+    if (c->prof && (rc = prof_event(c, true))) return rc;
+    // xbar_{t+1} (trainer.py:182) and the stamp of the end of round t's update; history[h - 1] rides the launch
+    const FoldArgs fold = fold_args(met ? h - 1 : 0);
+    HIPOK(launch_colsum(c->dtype, c->xs[c->cur ^ 1], c->n, c->ld, (int32_t)c->nchs, kRowsPerGroup, c->part,
+                        c->stamps + h + 1, n_div(c), c->xbar[xb ^ 1], nullptr, 0.0, 0, c->stream, c->S,
+                        met ? &fold : nullptr));
+    if (pass_loss && (rc = metrics_pass(c, c->xs[c->cur ^ 1], c->xbar[xb ^ 1], false, false, true))) return rc;
+    c->cur ^= 1;
+    c->ycur ^= 1;
+    xb ^= 1;
+  }
+  if (metrics) {  // the row of the last iterates; the column sums land in the spare xbar
+    const GtArgs g = gt_args(false, true);
+    if (want_cons || fuse_loss) HIPOK(launch_gt(c, true, g));
+    const FoldArgs fold = fold_args(T - 1);
+    HIPOK(launch_colsum(c->dtype, c->xs[c->cur], c->n, c->ld, (int32_t)c->nchs, kRowsPerGroup, c->part, nullptr,
+                        n_div(c), c->xbar[xb ^ 1], nullptr, 0.0, 0, c->stream, c->S, &fold));
+  }
+  return finish_run(c, T, T, lam_obj, f_opt, want_obj ? obj_out : nullptr, want_cons ? cons_out : nullptr,
+                    time_out);
+}
+
+}  // namespace
+
+int dopt_run_gt(dopt_ctx* c, int64_t t0, int64_t T, double eta0, int64_t batch, const int32_t* idx, double lam_grad,
+                double lam_obj, double f_opt, uint32_t flags, double* obj_out, double* cons_out,
+                double* time_out) {
+  return run_gt(c, t0, T, eta0, batch, idx, lam_grad, lam_obj, f_opt, flags, obj_out, cons_out, time_out);
+}
+
+int dopt_gt_set_state(dopt_ctx* c, const double* y, const double* g) {
+  CHECK_ARG(c, "ctx is NULL");
+  int rc;
+  if ((rc = check_gt(c))) return rc;
+  if ((rc = set_device(c))) return rc;
+  if ((rc = ensure_gt(c))) return rc;
+  const size_t st = (size_t)c->n * c->ld * c->esz;
+  if (y) {
+    if ((rc = upload_rows(c, c->dtype, y, 0, c->ys[c->ycur], c->n, c->d, c->ld))) return rc;
+  } else {
+    HIPOK(hipMemsetAsync(c->ys[c->ycur], 0, st, c->stream));
+  }
+  if (g) {
+    if ((rc = upload_rows(c, c->dtype, g, 0, c->gprev, c->n, c->d, c->ld))) return rc;
+  } else {
+    HIPOK(hipMemsetAsync(c->gprev, 0, st, c->stream));
+  }
+  HIPOK(hipStreamSynchronize(c->stream));
+  return DOPT_OK;
+}
+
+int dopt_gt_get_state(dopt_ctx* c, double* y, double* g) {
+  CHECK_ARG(c, "ctx is NULL");
+  int rc;
+  if ((rc = check_gt(c))) return rc;
+  if ((rc = set_device(c))) return rc;
+  if ((rc = ensure_gt(c))) return rc;
+  if (y && (rc = download_rows(c, c->dtype, c->ys[c->ycur], y, c->n, c->d, c->ld))) return rc;
+  if (g && (rc = download_rows(c, c->dtype, c->gprev, g, c->n, c->d, c->ld))) return rc;
+  return DOPT_OK;
 }
 
 // ---------------------------------------------------------------------------- single evaluations

@@ -24,6 +24,11 @@ Config keys beyond the reference's (all optional):
   mean_mixing_min  complete graphs of at least this many workers mix through the
                  column sums (default 128)
   distributed    False disables the multi-process mode below
+  algorithm  DecentralizedTrainer: 'dsgd' (default, the reference's round) or
+             'gradient_tracking' (DIGing / DSGT: every worker also carries a mixed tracker
+             y_i of the network-average gradient and steps along it,
+             y_i <- sum_j W_ij y_j + g_i(new) - g_i(old), x_i <- sum_j W_ij x_j - eta_t y_i;
+             one fused launch per round, single process, CSR mixing, no checkpoints)
 
 Multi-process mode: when torch.distributed is initialised with more than one rank
 (e.g. `python -m torch.distributed.run --nproc-per-node 8 main.py`), every rank
@@ -665,6 +670,10 @@ class DecentralizedTrainer:
         self.total_floats_transmitted = 0
         cfg = self.config
         lam_grad = _grad_reg(cfg, n_iterations, self.workers)
+        algorithm = cfg.get("algorithm", "dsgd")
+        if algorithm != "dsgd":
+            return self._run_gradient_tracking(algorithm, int(n_iterations), X_full, y_full, f_opt, lam_grad,
+                                               reg_param, start_time)
         info = _dist_info(cfg)
         if info is not None:
             return self._run_distributed(info, int(n_iterations), X_full, y_full, f_opt, lam_grad, reg_param,
@@ -712,6 +721,51 @@ class DecentralizedTrainer:
         self.loop_seconds = time.perf_counter() - loop_start
         models = eng.get_models()
         for i, worker in enumerate(self.workers):  # trainer.py:178-179: row views
+            worker.x = models[i, :]
+        _warn_nonfinite(self.history, self.config)
+        print(f"Decentralized ({self.topology}) training finished. Time: {time.time() - start_time:.2f}s")
+        final_avg_model = np.mean([worker.x for worker in self.workers], axis=0)
+        return self.history, final_avg_model
+
+    def _run_gradient_tracking(self, algorithm, T, X_full, y_full, f_opt, lam_grad, reg_param, start_time):
+        """config 'algorithm' = 'gradient_tracking': the rounds of Engine.run_gt in D-SGD's chunk loop,
+        from y = g = 0.  Every unsupported combination is refused before any device call."""
+        cfg = self.config
+        if algorithm != "gradient_tracking":
+            raise ValueError(f"unknown algorithm {algorithm!r}: 'dsgd' or 'gradient_tracking'")
+        if _dist_info(cfg) is not None:
+            raise NotImplementedError("gradient tracking runs in a single process (no multi-rank job)")
+        if self._mean_mixing() and self._topo.uniform_offdiag() is not None:
+            raise NotImplementedError("gradient tracking mixes through the CSR matrix: raise 'mean_mixing_min' "
+                                      "above the number of workers")
+        ck_keys = [k for k in ("checkpoint_path", "checkpoint_every", "resume_from") if cfg.get(k)]
+        if ck_keys:
+            raise NotImplementedError(f"gradient tracking does not checkpoint (config {ck_keys})")
+        if cfg.get("sampling", "legacy") == "device":
+            raise NotImplementedError("gradient tracking draws its minibatches on the host (sampling='legacy')")
+        eng = _engine(self.workers, self.n_features, cfg, X_full=X_full, y_full=y_full)
+        want_obj = _set_objective_data(eng, self.workers, self.n_features, X_full, y_full, _sampled_key(cfg))
+        t = self._topo
+        eng.set_topology(t.row_ptr, t.col, t.w)
+        eng.set_models(np.stack([np.asarray(w.x, dtype=np.float64) for w in self.workers]))
+        eng.gt_set_state(None, None)
+        iteration_transmission = 2 * np.sum(self.degrees) * self.n_features  # x and y both travel
+        eta0 = cfg["learning_rate_eta0"]
+        loop_start = time.perf_counter()
+        with closing(_index_chunks(self.workers, T, cfg)) as chunks:
+            for t0, n, b, idx, _ in chunks:
+                t_host = time.time() - start_time
+                obj, cons, tim = eng.run_gt(n, eta0, b, lam_grad, reg_param, f_opt, idx=idx, t0=t0,
+                                            objective=want_obj, consensus=True, want_time=True)
+                self.history["consensus_error"].extend(list(cons))
+                if want_obj:
+                    self.history["objective"].extend(list(obj))
+                self.history["time"].extend((tim + t_host).tolist())
+                for _ in range(n):
+                    self.total_floats_transmitted += iteration_transmission
+        self.loop_seconds = time.perf_counter() - loop_start
+        models = eng.get_models()
+        for i, worker in enumerate(self.workers):
             worker.x = models[i, :]
         _warn_nonfinite(self.history, self.config)
         print(f"Decentralized ({self.topology}) training finished. Time: {time.time() - start_time:.2f}s")

@@ -55,7 +55,9 @@ extern "C" {
  *   8  round 6: dopt_comm_create takes timeout_s -- the communicator is created non-blocking and its
  *      setup, a peer's first connection and its destroy are each bounded by that time.
  *   9  round 6: the pull transport (dopt_lagged_ipc_export / _import): the lagged exchange as a copy
- *      kernel of the engine's reading the peers' send slots through IPC handles, no RCCL kernel. */
+ *      kernel of the engine's reading the peers' send slots through IPC handles, no RCCL kernel.
+ *      Added under 9 (additions only, nothing changed): gradient tracking -- dopt_run_gt,
+ *      dopt_gt_set_state, dopt_gt_get_state. */
 #define DOPT_ABI_VERSION 9
 
 typedef struct dopt_ctx dopt_ctx;
@@ -230,6 +232,32 @@ int dopt_run_dsgd_pipelined(dopt_ctx *ctx, int64_t t0, int64_t T, double eta0, i
                             const int32_t *idx, double lam_grad, double lam_obj, double f_opt,
                             uint32_t flags, double *obj_out, double *cons_out, double *time_out,
                             int64_t *n_out);
+
+/* T rounds of gradient tracking (DIGing / DSGT), rounds t0..t0+T-1 -- the reference has no such
+ * trainer; the round replaces D-SGD's step along the worker's own gradient (trainer.py:173-175)
+ * by a step along a second mixed vector y_i that tracks the network-average gradient:
+ *   g_new_i = grad f_i(x_i; minibatch)   (worker.py:30-44, regulariser included; 0 for an empty shard)
+ *   y_i <- sum_j W_ij y_j + g_new_i - g_i
+ *   x_i <- sum_j W_ij x_j - eta0/sqrt(t+1) * y_i   (the NEW y_i)
+ *   g_i <- g_new_i
+ * i.e. x_{t+1} = W x_t - eta_t y_t, y_{t+1} = W y_t + g_{t+1} - g_t with y_0 = g_0, when y and g
+ * start at zero.  One fused launch per round on the device.  Same arguments and history as
+ * dopt_run_dsgd (objective at the mean of the new iterates, consensus error).  The call continues
+ * from the tracker state (y, g) on the context, so a run split into several calls is one chain
+ * (and gives the same bits as one call); loading or generating shards drops that state,
+ * dopt_set_models leaves it alone.  idx == NULL needs full-shard batches.
+ * DOPT_ERR_UNSUPPORTED: rows beyond the row-resident kernel (column-blocked contexts), mean mixing
+ * (dopt_set_mixing_mean; give the complete graph as CSR), a halo plan, the device sampler. */
+int dopt_run_gt(dopt_ctx *ctx, int64_t t0, int64_t T, double eta0, int64_t batch,
+                const int32_t *idx, double lam_grad, double lam_obj, double f_opt,
+                uint32_t flags, double *obj_out, double *cons_out, double *time_out);
+
+/* Tracker state of dopt_run_gt, N x d row-major float64 at the boundary like the iterates:
+ * y = the trackers, g = every worker's last stochastic gradient.  A NULL argument of
+ * dopt_gt_set_state sets that array to zero (NULL, NULL: a fresh chain); a NULL argument of
+ * dopt_gt_get_state is skipped. */
+int dopt_gt_set_state(dopt_ctx *ctx, const double *y, const double *g);
+int dopt_gt_get_state(dopt_ctx *ctx, double *y, double *g);
 
 /* T rounds of CentralizedTrainer.run (trainer.py:41-71): every worker's
  * gradient at the shared iterate, their mean, one step; objective at the
