@@ -67,6 +67,9 @@ _SIGS = {
     "dopt_run_gt": ([_P, _I64, _I64, _D, _I64, _P, _D, _D, _D, ctypes.c_uint32, _P, _P, _P], ctypes.c_int),
     "dopt_gt_set_state": ([_P, _P, _P], ctypes.c_int),
     "dopt_gt_get_state": ([_P, _P, _P], ctypes.c_int),
+    "dopt_run_choco": ([_P, _I64, _I64, _D, _I64, _P, _D, _D, _D, ctypes.c_uint32, _I64, _D, _P, _P, _P], ctypes.c_int),
+    "dopt_choco_set_state": ([_P, _P], ctypes.c_int),
+    "dopt_choco_get_state": ([_P, _P], ctypes.c_int),
     "dopt_run_centralized": ([_P, _I64, _I64, _D, _I64, _P, _D, _D, _D, ctypes.c_uint32, _P, _P], ctypes.c_int),
     "dopt_eval_gradient": ([_P, ctypes.c_int, _I64, _I64, _P, _P, _P, _D, _P], ctypes.c_int),
     "dopt_eval_objective": ([_P, ctypes.c_int, _I64, _I64, _P, _P, _P, _D, _P], ctypes.c_int),
@@ -464,6 +467,33 @@ class Engine:
         g = np.empty((self.n, self.d), dtype=np.float64)
         check(lib().dopt_gt_get_state(self._h, _ptr(y), _ptr(g)))
         return y, g
+
+    def run_choco(self, rounds, eta0, batch, lam_grad, lam_obj, f_opt=0.0, *, k, gamma, idx=None, t0=0,
+                  objective=True, consensus=True, want_time=False):
+        """dopt_run_choco: rounds of CHOCO-SGD (each worker sends the k largest entries of
+        x_i - xhat_i, consensus step gamma) from the public copies on the context; the other
+        arguments as run_gt.  Returns (objective, consensus) histories, plus the times if asked."""
+        T = int(rounds)
+        obj = np.zeros(T) if objective else None
+        cons = np.zeros(T) if consensus else None
+        tim = np.zeros(T) if want_time else None
+        if idx is not None:
+            idx = np.ascontiguousarray(idx, dtype=np.int32)
+        flags = (RUN_OBJECTIVE if objective else 0) | (RUN_CONSENSUS if consensus else 0)
+        check(lib().dopt_run_choco(self._h, int(t0), T, float(eta0), int(batch), _ptr(idx), float(lam_grad),
+                                   float(lam_obj), float(f_opt), flags, int(k), float(gamma), _ptr(obj), _ptr(cons),
+                                   _ptr(tim)))
+        return (obj, cons, tim) if want_time else (obj, cons)
+
+    def choco_set_state(self, xhat=None):
+        """Public copies xhat (N x d); None = zeros."""
+        xhat = None if xhat is None else np.ascontiguousarray(xhat, dtype=np.float64).reshape(self.n, self.d)
+        check(lib().dopt_choco_set_state(self._h, _ptr(xhat)))
+
+    def choco_get_state(self):
+        xhat = np.empty((self.n, self.d), dtype=np.float64)
+        check(lib().dopt_choco_get_state(self._h, _ptr(xhat)))
+        return xhat
 
     def run_centralized(self, T, eta0, batch, lam_grad, lam_obj, f_opt=0.0, idx=None, t0=0,
                         objective=True, want_time=True):

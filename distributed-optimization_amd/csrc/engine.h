@@ -256,6 +256,24 @@ hipError_t launch_gt_f32(int problem, int cpl, bool met, const GtArgs& a, int n_
 hipError_t launch_gt_f64(int problem, int cpl, bool met, const GtArgs& a, int n_workers, hipStream_t s);
 hipError_t launch_gt_x32(int problem, int cpl, bool met, const GtArgs& a, int n_workers, hipStream_t s);
 
+// ---- CHOCO-SGD (k_round_choco.inc): top-k compressed gossip with error feedback, one launch per
+// round, one workgroup per worker
+//   x_new_i = x_i - eta g_i + gamma (sum_j W_ij xhat_j - xhat_i),   xhat_i <- xhat_i + top_k(x_new_i - xhat_i)
+// r and r.flags as in GtArgs: F_STEP (without it metrics only: no mix, no selection, no store), F_CONS,
+// and -- full-shard batches only -- F_LOSS.  No halo rows, no F_MEAN.
+struct ChocoArgs {
+  RoundArgs r;
+  const void* xhat_old;  // [n x ld] T public copies before the round (read only during the round)
+  void* xhat_new;        // [n x ld] T public copies after the round
+  int32_t k;             // entries of x_new_i - xhat_i kept per worker, 1 <= k <= d
+  double gamma;          // consensus step size, 0 < gamma <= 1
+  int32_t wave_hist;     // A/B: one selection sub-histogram per wave instead of one shared histogram (same bits)
+};
+// per element-type pair (choco_f32.hip / choco_f64.hip / choco_x32.hip); cpl = 16-byte DATA chunks per lane
+hipError_t launch_choco_f32(int problem, int cpl, bool met, const ChocoArgs& a, int n_workers, hipStream_t s);
+hipError_t launch_choco_f64(int problem, int cpl, bool met, const ChocoArgs& a, int n_workers, hipStream_t s);
+hipError_t launch_choco_x32(int problem, int cpl, bool met, const ChocoArgs& a, int n_workers, hipStream_t s);
+
 // ---- large d (column-blocked): one workgroup per (worker, group of 64-chunk column blocks)
 constexpr int kSplitMaxRows = 64;  // rows held in registers by a step workgroup (16 per wave)
 // Step: g_i = (1/nb) sum_k coef_k x_k + lam x_i, x_i' = mix - eta g_i (block by block); with

@@ -13,6 +13,7 @@
 //   rp/ci/cw                CSR mixing matrix (diagonal included), cw in T
 //   G      [N x ld]     T   per-worker gradients (centralized trainer, multi-GPU phases)
 //   ys[2], gprev [N x ld] T   gradient tracking: tracker ping-pong, previous stochastic gradients
+//   xh[2]  [N x ld]     T   CHOCO-SGD: ping-pong of the public copies xhat
 //
 // Launch schedule of one D-SGD round t (metrics every round):
 //   k_round(t)       grad + mix + step for every worker, and the consensus /
@@ -21,7 +22,8 @@
 //   k_colsum_part(t) + k_colsum_final(t)   xbar_{t+1}; one extra block folds history[t-1]
 // plus one metrics-only pass after the last round.  Only a separate objective dataset
 // (X_full that is not the shards) takes a metrics-only pass every round.
-// A gradient-tracking round (dopt_run_gt) has the same schedule with k_round_gt in k_round's place.
+// A gradient-tracking round (dopt_run_gt) has the same schedule with k_round_gt in k_round's place,
+// a CHOCO-SGD round (dopt_run_choco) with k_round_choco.
 // The multi-GPU phase functions (dopt_phase_*) split the same round at its
 // communication points; distributed.py drives them.
 #include <hip/hip_runtime.h>
@@ -146,6 +148,9 @@ struct dopt_ctx {
   void* ys[2] = {nullptr, nullptr};
   int ycur = 0;
   void* gprev = nullptr;
+  // CHOCO-SGD (dopt_run_choco): ping-pong of the public copies, [N x ld] T, allocated (zero) on first use
+  void* xh[2] = {nullptr, nullptr};
+  int hcur = 0;
   void* xbar[2] = {nullptr, nullptr};
   int xb = 0;  // xbar[xb] = average of the current iterates
   double* S = nullptr;             // [ld] column sums of the current iterates (complete-graph mixing)
@@ -485,6 +490,9 @@ int alloc_state(dopt_ctx* c) {
   dfree(c->ys[1]);
   dfree(c->gprev);
   c->ycur = 0;
+  dfree(c->xh[0]);  // ... and so are the public copies of dopt_run_choco
+  dfree(c->xh[1]);
+  c->hcur = 0;
   c->cur = 0;
   c->gcur = 0;
   c->xb = 0;
@@ -1341,7 +1349,7 @@ int dopt_destroy(dopt_ctx* c) {
   if (c->stream) (void)hipStreamSynchronize(c->stream);
   if (c->own_stream) (void)hipStreamSynchronize(c->own_stream);
   for (void** p : {&c->X, &c->y, &c->Xo, &c->yo, &c->xs[0], &c->xs[1], &c->xg[0], &c->xg[1], &c->G, &c->ys[0], &c->ys[1],
-                   &c->gprev, &c->xbar[0], &c->xbar[1], &c->cw, &c->staging, &c->sx, &c->wdiag, &c->coef})
+                   &c->gprev, &c->xh[0], &c->xh[1], &c->xbar[0], &c->xbar[1], &c->cw, &c->staging, &c->sx, &c->wdiag, &c->coef})
     dfree(*p);
   dfree_t(c->off);
   dfree_t(c->offo);
@@ -2001,6 +2009,171 @@ int dopt_gt_get_state(dopt_ctx* c, double* y, double* g) {
   if (y && (rc = download_rows(c, c->dtype, c->ys[c->ycur], y, c->n, c->d, c->ld))) return rc;
   if (g && (rc = download_rows(c, c->dtype, c->gprev, g, c->n, c->d, c->ld))) return rc;
   return DOPT_OK;
+}
+
+// ---------------------------------------------------------------------------- CHOCO-SGD
+namespace {
+
+// Public copies of dopt_run_choco: xhat = 0 until a run or dopt_choco_set_state says otherwise.
+int ensure_choco(dopt_ctx* c) {
+  if (c->xh[0] && c->xh[1]) return DOPT_OK;
+  const size_t st = (size_t)std::max<int64_t>(1, c->n) * c->ld * c->esz;
+  int rc;
+  for (void** p : {&c->xh[0], &c->xh[1]}) {
+    if ((rc = dalloc(p, st))) return rc;
+    HIPOK(hipMemsetAsync(*p, 0, st, c->stream));
+  }
+  c->hcur = 0;
+  return DOPT_OK;
+}
+
+hipError_t launch_choco(dopt_ctx* c, bool met, const ChocoArgs& g) {
+  if (c->dtype == DOPT_F32) return launch_choco_f32(c->problem, c->cpl, met, g, (int)c->n, c->stream);
+  if (c->xdtype == DOPT_F32) return launch_choco_x32(c->problem, c->cpl, met, g, (int)c->n, c->stream);
+  return launch_choco_f64(c->problem, c->cpl, met, g, (int)c->n, c->stream);
+}
+
+int check_choco(dopt_ctx* c) {
+  if (!c->have_data) return fail(DOPT_ERR_STATE, "no shards loaded");
+  if (c->split)
+    return fail(DOPT_ERR_UNSUPPORTED, "CHOCO: rows of %lld elements are column-blocked; the compressed round holds a "
+                "row per wave (at most %d 16-byte chunks per lane)", (long long)c->d,
+                max_chunks_per_lane(c->dtype, c->xdtype));
+  return DOPT_OK;
+}
+
+// T rounds of CHOCO-SGD, modelled on run_gt: k_round_choco, then the column sums of the new iterates
+// with the history row of the previous round folded in; round h's launch takes the metrics of x_h at
+// xbar_h (history[h - 1]) in its row pass, and the row of the last iterates takes one more launch of
+// the same kernel without the step, folded by the same column-sum launch -- so a run split into
+// several calls gives the bits of one call.  Host minibatches (idx) and a separate objective
+// dataset: the kernel fuses the consensus only and the objective takes the metrics-only pass.
+int run_choco(dopt_ctx* c, int64_t t0, int64_t T, double eta0, int64_t batch, const int32_t* idx, double lam_grad,
+              double lam_obj, double f_opt, uint32_t flags, int64_t k, double gamma, double* obj_out, double* cons_out,
+              double* time_out) {
+  CHECK_ARG(c, "ctx is NULL");
+  int rc;
+  if ((rc = check_choco(c))) return rc;
+  if (!c->have_topo) return fail(DOPT_ERR_STATE, "no topology set");
+  if (c->mean_mix)
+    return fail(DOPT_ERR_UNSUPPORTED, "CHOCO: mean mixing (dopt_set_mixing_mean) is not supported; give the complete "
+                "graph as CSR (dopt_set_topology)");
+  if (c->n_halo > 0 || c->n_send > 0 || c->sptr)
+    return fail(DOPT_ERR_UNSUPPORTED, "CHOCO: contexts with a halo plan (multi-GPU slices) are not supported");
+  if (!idx && batch < c->max_m && c->sampler == DOPT_SAMPLE_DEVICE)
+    return fail(DOPT_ERR_UNSUPPORTED, "CHOCO: the device sampler is not supported; pass idx");
+  if (!(k >= 1 && k <= c->d))
+    return fail(DOPT_ERR_INVALID, "CHOCO: k = %lld outside [1, d = %lld]", (long long)k, (long long)c->d);
+  if (!(gamma > 0.0 && gamma <= 1.0)) return fail(DOPT_ERR_INVALID, "CHOCO: gamma = %g outside (0, 1]", gamma);
+  if ((rc = check_run(c, T, batch, idx, true))) return rc;
+  if ((rc = set_device(c))) return rc;
+  if ((rc = rs_end(c))) return rc;
+  c->carry_pending = false;
+  c->send_fresh = false;
+  if (T == 0) return DOPT_OK;
+  if ((rc = ensure_hist(c, T + 1))) return rc;
+  if ((rc = ensure_choco(c))) return rc;
+  const bool want_obj = flags & DOPT_RUN_OBJECTIVE, want_cons = flags & DOPT_RUN_CONSENSUS;
+  const bool metrics = want_obj || want_cons;
+  const bool fuse_loss = want_obj && !idx && !c->obj_sep;  // the pass walks every objective row
+  const bool pass_loss = want_obj && !fuse_loss;
+  const char* wh_env = getenv("DOPT_CHOCO_WAVEHIST");  // A/B knob, read per call: 1 = a sub-histogram per wave (same bits)
+  const bool wave_hist = wh_env && atoi(wh_env) != 0;
+  const int64_t CH = idx ? idx_chunk_rounds(c, T, batch) : 1;
+  int& xb = c->xb;
+  if ((rc = colsum_current(c))) return rc;  // xbar of the starting iterates
+  HIPOK(launch_stamp(c->stamps, c->stream));
+
+  auto choco_args = [&](bool step, bool met) {
+    ChocoArgs g;
+    memset(&g, 0, sizeof(g));
+    g.r = base_args(c);
+    g.r.x_old = c->xs[c->cur];
+    g.r.x_new = c->xs[c->cur ^ 1];
+    g.r.xbar = c->xbar[xb];
+    g.r.lam = lam_grad;
+    g.r.b = batch;
+    g.r.flags |= (step ? F_STEP : 0) | (met && want_cons ? F_CONS : 0) | (met && fuse_loss ? F_LOSS : 0);
+    g.xhat_old = c->xh[c->hcur];
+    g.xhat_new = c->xh[c->hcur ^ 1];
+    g.k = (int32_t)k;
+    g.gamma = gamma;
+    g.wave_hist = wave_hist ? 1 : 0;
+    if (g.r.flags & F_LOSS) c->loss_groups = c->n;  // per-worker loss slabs
+    return g;
+  };
+  // history row `row` = the slabs of the current launch (and, pass_loss, of the last metrics pass) at xbar[xb]
+  auto fold_args = [&](int64_t row) {
+    double* hr = c->hraw + 3 * row;
+    return FoldArgs{want_cons ? c->slab_cons : nullptr, c->n, want_obj ? c->slab_loss : nullptr, c->loss_groups,
+                    want_obj ? c->xbar[xb] : nullptr, hr, hr + 1, hr + 2};
+  };
+
+  for (int64_t h = 0; h < T; ++h) {
+    const int64_t t = t0 + h;
+    if (idx && h % CH == 0) {
+      if ((rc = upload_idx_chunk(c, idx, h, std::min(CH, T - h), batch))) return rc;
+    }
+    const bool met = metrics && h > 0;
+    ChocoArgs g = choco_args(true, met);
+    g.r.idx = idx ? c->idx + (h % CH) * c->n * batch : nullptr;
+    g.r.eta = eta0 / sqrt((double)(t + 1));  // trainer.py:138-140
+    if (c->prof && (rc = prof_event(c, false))) return rc;
+    HIPOK(launch_choco(c, metrics, g));
+    if (c->prof && (rc = prof_event(c, true))) return rc;
+    // xbar_{t+1} (trainer.py:182) and the stamp of the end of round t's update; history[h - 1] rides the launch
+    const FoldArgs fold = fold_args(met ? h - 1 : 0);
+    HIPOK(launch_colsum(c->dtype, c->xs[c->cur ^ 1], c->n, c->ld, (int32_t)c->nchs, kRowsPerGroup, c->part,
+                        c->stamps + h + 1, n_div(c), c->xbar[xb ^ 1], nullptr, 0.0, 0, c->stream, c->S,
+                        met ? &fold : nullptr));
+    if (pass_loss && (rc = metrics_pass(c, c->xs[c->cur ^ 1], c->xbar[xb ^ 1], false, false, true))) return rc;
+    c->cur ^= 1;
+    c->hcur ^= 1;
+    xb ^= 1;
+  }
+  if (metrics) {  // the row of the last iterates; the column sums land in the spare xbar
+    const ChocoArgs g = choco_args(false, true);
+    if (want_cons || fuse_loss) HIPOK(launch_choco(c, true, g));
+    const FoldArgs fold = fold_args(T - 1);
+    HIPOK(launch_colsum(c->dtype, c->xs[c->cur], c->n, c->ld, (int32_t)c->nchs, kRowsPerGroup, c->part, nullptr,
+                        n_div(c), c->xbar[xb ^ 1], nullptr, 0.0, 0, c->stream, c->S, &fold));
+  }
+  return finish_run(c, T, T, lam_obj, f_opt, want_obj ? obj_out : nullptr, want_cons ? cons_out : nullptr,
+                    time_out);
+}
+
+}  // namespace
+
+int dopt_run_choco(dopt_ctx* c, int64_t t0, int64_t T, double eta0, int64_t batch, const int32_t* idx,
+                   double lam_grad, double lam_obj, double f_opt, uint32_t flags, int64_t k, double gamma,
+                   double* obj_out, double* cons_out, double* time_out) {
+  return run_choco(c, t0, T, eta0, batch, idx, lam_grad, lam_obj, f_opt, flags, k, gamma, obj_out, cons_out,
+                   time_out);
+}
+
+int dopt_choco_set_state(dopt_ctx* c, const double* xhat) {
+  CHECK_ARG(c, "ctx is NULL");
+  int rc;
+  if ((rc = check_choco(c))) return rc;
+  if ((rc = set_device(c))) return rc;
+  if ((rc = ensure_choco(c))) return rc;
+  if (xhat) {
+    if ((rc = upload_rows(c, c->dtype, xhat, 0, c->xh[c->hcur], c->n, c->d, c->ld))) return rc;
+  } else {
+    HIPOK(hipMemsetAsync(c->xh[c->hcur], 0, (size_t)c->n * c->ld * c->esz, c->stream));
+  }
+  HIPOK(hipStreamSynchronize(c->stream));
+  return DOPT_OK;
+}
+
+int dopt_choco_get_state(dopt_ctx* c, double* xhat) {
+  CHECK_ARG(c, "ctx is NULL");
+  CHECK_ARG(xhat, "xhat is NULL");
+  int rc;
+  if ((rc = check_choco(c))) return rc;
+  if ((rc = set_device(c))) return rc;
+  if ((rc = ensure_choco(c))) return rc;
+  return download_rows(c, c->dtype, c->xh[c->hcur], xhat, c->n, c->d, c->ld);
 }
 
 // ---------------------------------------------------------------------------- single evaluations

@@ -28,7 +28,14 @@ Config keys beyond the reference's (all optional):
              'gradient_tracking' (DIGing / DSGT: every worker also carries a mixed tracker
              y_i of the network-average gradient and steps along it,
              y_i <- sum_j W_ij y_j + g_i(new) - g_i(old), x_i <- sum_j W_ij x_j - eta_t y_i;
-             one fused launch per round, single process, CSR mixing, no checkpoints)
+             one fused launch per round, single process, CSR mixing, no checkpoints) or
+             'choco' (CHOCO-SGD, top-k compressed gossip with error feedback: the workers
+             mix through public copies xhat_i, x_i <- x_i - eta_t g_i + choco_gamma
+             (sum_j W_ij xhat_j - xhat_i), and send only the compression_k largest entries of
+             x_i - xhat_i, which the receivers add to xhat_i; same restrictions)
+  compression_k  algorithm='choco', required: entries sent per worker and round, an int in
+             [1, n_features]
+  choco_gamma    algorithm='choco', required: the consensus step size, a float in (0, 1]
 
 Multi-process mode: when torch.distributed is initialised with more than one rank
 (e.g. `python -m torch.distributed.run --nproc-per-node 8 main.py`), every rank
@@ -671,6 +678,8 @@ class DecentralizedTrainer:
         cfg = self.config
         lam_grad = _grad_reg(cfg, n_iterations, self.workers)
         algorithm = cfg.get("algorithm", "dsgd")
+        if algorithm == "choco":
+            return self._run_choco(int(n_iterations), X_full, y_full, f_opt, lam_grad, reg_param, start_time)
         if algorithm != "dsgd":
             return self._run_gradient_tracking(algorithm, int(n_iterations), X_full, y_full, f_opt, lam_grad,
                                                reg_param, start_time)
@@ -732,7 +741,7 @@ class DecentralizedTrainer:
         from y = g = 0.  Every unsupported combination is refused before any device call."""
         cfg = self.config
         if algorithm != "gradient_tracking":
-            raise ValueError(f"unknown algorithm {algorithm!r}: 'dsgd' or 'gradient_tracking'")
+            raise ValueError(f"unknown algorithm {algorithm!r}: 'dsgd', 'gradient_tracking' or 'choco'")
         if _dist_info(cfg) is not None:
             raise NotImplementedError("gradient tracking runs in a single process (no multi-rank job)")
         if self._mean_mixing() and self._topo.uniform_offdiag() is not None:
@@ -763,6 +772,56 @@ class DecentralizedTrainer:
                 self.history["time"].extend((tim + t_host).tolist())
                 for _ in range(n):
                     self.total_floats_transmitted += iteration_transmission
+        self.loop_seconds = time.perf_counter() - loop_start
+        models = eng.get_models()
+        for i, worker in enumerate(self.workers):
+            worker.x = models[i, :]
+        _warn_nonfinite(self.history, self.config)
+        print(f"Decentralized ({self.topology}) training finished. Time: {time.time() - start_time:.2f}s")
+        final_avg_model = np.mean([worker.x for worker in self.workers], axis=0)
+        return self.history, final_avg_model
+
+    def _run_choco(self, T, X_full, y_full, f_opt, lam_grad, reg_param, start_time):
+        """config 'algorithm' = 'choco': the rounds of Engine.run_choco in D-SGD's chunk loop, from
+        xhat = 0.  A worker sends each neighbour the compression_k kept entries of x_i - xhat_i as
+        (index, value) pairs, so total_floats_transmitted grows per round by
+        2 * compression_k * sum(degrees): one value and one index per kept entry per directed edge.
+        Bad keys and every unsupported combination are refused before any device call."""
+        cfg = self.config
+        k, gamma = cfg.get("compression_k"), cfg.get("choco_gamma")
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= k <= self.n_features:
+            raise ValueError(f"CHOCO needs config 'compression_k', an int in [1, {self.n_features}]: got {k!r}")
+        if isinstance(gamma, bool) or not isinstance(gamma, (int, float, np.floating)) or not 0 < gamma <= 1:
+            raise ValueError(f"CHOCO needs config 'choco_gamma', a float in (0, 1]: got {gamma!r}")
+        if _dist_info(cfg) is not None:
+            raise NotImplementedError("CHOCO runs in a single process (no multi-rank job)")
+        if self._mean_mixing() and self._topo.uniform_offdiag() is not None:
+            raise NotImplementedError("CHOCO mixes through the CSR matrix: raise 'mean_mixing_min' above the "
+                                      "number of workers")
+        ck_keys = [key for key in ("checkpoint_path", "checkpoint_every", "resume_from") if cfg.get(key)]
+        if ck_keys:
+            raise NotImplementedError(f"CHOCO does not checkpoint (config {ck_keys})")
+        if cfg.get("sampling", "legacy") == "device":
+            raise NotImplementedError("CHOCO draws its minibatches on the host (sampling='legacy')")
+        eng = _engine(self.workers, self.n_features, cfg, X_full=X_full, y_full=y_full)
+        want_obj = _set_objective_data(eng, self.workers, self.n_features, X_full, y_full, _sampled_key(cfg))
+        t = self._topo
+        eng.set_topology(t.row_ptr, t.col, t.w)
+        eng.set_models(np.stack([np.asarray(w.x, dtype=np.float64) for w in self.workers]))
+        eng.choco_set_state(None)
+        iteration_transmission = 2 * int(k) * np.sum(self.degrees)
+        eta0 = cfg["learning_rate_eta0"]
+        loop_start = time.perf_counter()
+        with closing(_index_chunks(self.workers, T, cfg)) as chunks:
+            for t0, n, b, idx, _ in chunks:
+                t_host = time.time() - start_time
+                obj, cons, tim = eng.run_choco(n, eta0, b, lam_grad, reg_param, f_opt, k=int(k), gamma=float(gamma),
+                                               idx=idx, t0=t0, objective=want_obj, consensus=True, want_time=True)
+                self.history["consensus_error"].extend(list(cons))
+                if want_obj:
+                    self.history["objective"].extend(list(obj))
+                self.history["time"].extend((tim + t_host).tolist())
+                self.total_floats_transmitted += n * iteration_transmission
         self.loop_seconds = time.perf_counter() - loop_start
         models = eng.get_models()
         for i, worker in enumerate(self.workers):

@@ -57,7 +57,8 @@ extern "C" {
  *   9  round 6: the pull transport (dopt_lagged_ipc_export / _import): the lagged exchange as a copy
  *      kernel of the engine's reading the peers' send slots through IPC handles, no RCCL kernel.
  *      Added under 9 (additions only, nothing changed): gradient tracking -- dopt_run_gt,
- *      dopt_gt_set_state, dopt_gt_get_state. */
+ *      dopt_gt_set_state, dopt_gt_get_state; CHOCO-SGD -- dopt_run_choco, dopt_choco_set_state,
+ *      dopt_choco_get_state. */
 #define DOPT_ABI_VERSION 9
 
 typedef struct dopt_ctx dopt_ctx;
@@ -258,6 +259,36 @@ int dopt_run_gt(dopt_ctx *ctx, int64_t t0, int64_t T, double eta0, int64_t batch
  * dopt_gt_get_state is skipped. */
 int dopt_gt_set_state(dopt_ctx *ctx, const double *y, const double *g);
 int dopt_gt_get_state(dopt_ctx *ctx, double *y, double *g);
+
+/* T rounds of CHOCO-SGD (top-k compressed gossip with error feedback), rounds t0..t0+T-1 -- the
+ * reference has no such trainer; the round extends D-SGD's (trainer.py:173-175): the workers mix
+ * through public copies xhat_i of their iterates instead of the iterates themselves, and a worker
+ * sends only the k largest entries of x_i - xhat_i:
+ *   g_i     = grad f_i(x_i; minibatch)   (worker.py:30-44, regulariser included; 0 for an empty shard)
+ *   x_i    <- x_i - eta0/sqrt(t+1) * g_i + gamma (sum_j W_ij xhat_j - xhat_i)   (the OLD public copies)
+ *   q_i     = top_k(x_i - xhat_i)        (the NEW x_i; the k entries of largest magnitude, equal
+ *                                         magnitudes by lower column index, the rest 0)
+ *   xhat_i <- xhat_i + q_i
+ * With k = d and gamma = 1 this is x <- W (x - eta g) up to rounding.  One fused launch per round
+ * on the device; the selection is an exact radix select, so two runs give the same bits.  Same
+ * arguments and history as dopt_run_dsgd (objective at the mean of the new iterates, consensus
+ * error), plus k and gamma.  The call continues from the public copies on the context, so a run
+ * split into several calls is one chain (and gives the same bits as one call); loading or
+ * generating shards drops that state, dopt_set_models leaves it alone.  idx == NULL needs
+ * full-shard batches.
+ * DOPT_ERR_INVALID: k outside [1, d], gamma outside (0, 1].
+ * DOPT_ERR_UNSUPPORTED: rows beyond the row-resident kernel (column-blocked contexts), mean mixing
+ * (dopt_set_mixing_mean; give the complete graph as CSR), a halo plan, the device sampler. */
+int dopt_run_choco(dopt_ctx *ctx, int64_t t0, int64_t T, double eta0, int64_t batch,
+                   const int32_t *idx, double lam_grad, double lam_obj, double f_opt,
+                   uint32_t flags, int64_t k, double gamma, double *obj_out, double *cons_out,
+                   double *time_out);
+
+/* Public copies xhat of dopt_run_choco, N x d row-major float64 at the boundary like the iterates
+ * (dopt_set_models / dopt_get_models, which they extend).  xhat == NULL in dopt_choco_set_state
+ * sets them to zero (a fresh chain). */
+int dopt_choco_set_state(dopt_ctx *ctx, const double *xhat);
+int dopt_choco_get_state(dopt_ctx *ctx, double *xhat);
 
 /* T rounds of CentralizedTrainer.run (trainer.py:41-71): every worker's
  * gradient at the shared iterate, their mean, one step; objective at the
