@@ -21,12 +21,12 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("DOPT_LIB", os.path.join(_HERE, "libdopt.so"))
 
 OK, ERR_INVALID, ERR_HIP, ERR_STATE, ERR_UNSUPPORTED, ERR_COMM, ERR_NOMEM, ERR_RUNTIME = 0, -1, -2, -3, -4, -5, -6, -7
-LOGISTIC, QUADRATIC = 0, 1
+LOGISTIC, QUADRATIC, SOFTMAX = 0, 1, 2
 F32, F64 = 0, 1
 RUN_OBJECTIVE, RUN_CONSENSUS = 1, 2
 SAMPLE_HOST, SAMPLE_DEVICE = 0, 1
 MAX_BIP_ROWS = 65536  # dopt.h DOPT_MAX_BIP_ROWS: minibatch gradient inside the metrics pass
-PROBLEMS = {"logistic": LOGISTIC, "quadratic": QUADRATIC}
+PROBLEMS = {"logistic": LOGISTIC, "quadratic": QUADRATIC, "softmax": SOFTMAX}
 DTYPES = {"float32": F32, "fp32": F32, "f32": F32, np.float32: F32,
           "float64": F64, "fp64": F64, "f64": F64, np.float64: F64}
 
@@ -70,6 +70,10 @@ _SIGS = {
     "dopt_run_choco": ([_P, _I64, _I64, _D, _I64, _P, _D, _D, _D, ctypes.c_uint32, _I64, _D, _P, _P, _P], ctypes.c_int),
     "dopt_choco_set_state": ([_P, _P], ctypes.c_int),
     "dopt_choco_get_state": ([_P, _P], ctypes.c_int),
+    "dopt_load_shards_softmax": ([_P, _I64, _I64, _I64, _P, _P, _P, ctypes.c_int], ctypes.c_int),
+    "dopt_run_softmax": ([_P, _I64, _I64, _D, _I64, _P, _D, _D, _D, ctypes.c_uint32, _P, _P, _P], ctypes.c_int),
+    "dopt_softmax_set_models": ([_P, _P], ctypes.c_int),
+    "dopt_softmax_get_models": ([_P, _P], ctypes.c_int),
     "dopt_run_centralized": ([_P, _I64, _I64, _D, _I64, _P, _D, _D, _D, ctypes.c_uint32, _P, _P], ctypes.c_int),
     "dopt_eval_gradient": ([_P, ctypes.c_int, _I64, _I64, _P, _P, _P, _D, _P], ctypes.c_int),
     "dopt_eval_objective": ([_P, ctypes.c_int, _I64, _I64, _P, _P, _P, _D, _P], ctypes.c_int),
@@ -340,7 +344,9 @@ class Engine:
             pass
 
     # -- data
-    def load_shards(self, problem, X, y, shard_offsets):
+    def load_shards(self, problem, X, y, shard_offsets, n_classes=None):
+        """problem "softmax" takes n_classes (labels y in {0 .. n_classes - 1}) and makes the context a softmax
+        context: run_softmax / softmax_set_models / softmax_get_models are its rounds and iterates."""
         X = np.ascontiguousarray(X)
         src_f32 = 1 if X.dtype == np.float32 else 0
         X = np.ascontiguousarray(X, dtype=np.float32 if src_f32 else np.float64)
@@ -348,7 +354,15 @@ class Engine:
         off = np.ascontiguousarray(shard_offsets, dtype=np.int64)
         n = len(off) - 1
         d = X.shape[1]
-        check(lib().dopt_load_shards(self._h, PROBLEMS[problem], n, d, _ptr(off), _ptr(X), _ptr(y), src_f32))
+        if problem == "softmax":
+            if n_classes is None:
+                raise ValueError("load_shards('softmax', ...) needs n_classes")
+            check(lib().dopt_load_shards_softmax(self._h, n, d, int(n_classes), _ptr(off), _ptr(X), _ptr(y), src_f32))
+            self.n_classes = int(n_classes)
+        else:
+            if n_classes is not None:
+                raise ValueError("n_classes belongs to problem 'softmax'")
+            check(lib().dopt_load_shards(self._h, PROBLEMS[problem], n, d, _ptr(off), _ptr(X), _ptr(y), src_f32))
         self.n, self.d, self.problem = n, d, problem
         self.shard_rows = np.diff(off)
 
@@ -494,6 +508,32 @@ class Engine:
         xhat = np.empty((self.n, self.d), dtype=np.float64)
         check(lib().dopt_choco_get_state(self._h, _ptr(xhat)))
         return xhat
+
+    def run_softmax(self, T, eta0, batch, lam_grad, lam_obj, f_opt=0.0, idx=None, t0=0,
+                    objective=True, consensus=True, want_time=True):
+        """dopt_run_softmax: T rounds of softmax-regression D-SGD on a softmax context; arguments and
+        return value as run_dsgd."""
+        T = int(T)
+        obj = np.zeros(T) if objective else None
+        cons = np.zeros(T) if consensus else None
+        tim = np.zeros(T) if want_time else None
+        if idx is not None:
+            idx = np.ascontiguousarray(idx, dtype=np.int32)
+        flags = (RUN_OBJECTIVE if objective else 0) | (RUN_CONSENSUS if consensus else 0)
+        check(lib().dopt_run_softmax(self._h, int(t0), T, float(eta0), int(batch), _ptr(idx), float(lam_grad),
+                                     float(lam_obj), float(f_opt), flags, _ptr(obj), _ptr(cons), _ptr(tim)))
+        return obj, cons, tim
+
+    def softmax_set_models(self, x=None):
+        """Iterates of a softmax context (N x C x d); None = zeros."""
+        if x is not None:
+            x = np.ascontiguousarray(x, dtype=np.float64).reshape(self.n, self.n_classes, self.d)
+        check(lib().dopt_softmax_set_models(self._h, _ptr(x)))
+
+    def softmax_get_models(self):
+        x = np.empty((self.n, self.n_classes, self.d), dtype=np.float64)
+        check(lib().dopt_softmax_get_models(self._h, _ptr(x)))
+        return x
 
     def run_centralized(self, T, eta0, batch, lam_grad, lam_obj, f_opt=0.0, idx=None, t0=0,
                         objective=True, want_time=True):

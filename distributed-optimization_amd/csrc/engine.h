@@ -274,6 +274,24 @@ hipError_t launch_choco_f32(int problem, int cpl, bool met, const ChocoArgs& a, 
 hipError_t launch_choco_f64(int problem, int cpl, bool met, const ChocoArgs& a, int n_workers, hipStream_t s);
 hipError_t launch_choco_x32(int problem, int cpl, bool met, const ChocoArgs& a, int n_workers, hipStream_t s);
 
+// ---- softmax regression (k_round_softmax.inc): the D-SGD round of the multinomial logistic objective
+// on the matrix cores, one launch per round, one workgroup per worker
+//   G_i = (1/b) sum_k (softmax(W_i x_k) - e_{y_k}) x_k^T + lam W_i,   W_i' = sum_j Wmix_ij W_j - eta G_i
+// r: the D-SGD round's arguments with STATE rows of n_classes * r.ld elements, class-major (x_old / x_new
+// [n x C ld], xbar [C ld]); r.ld, r.nchunks: the data row.  r.flags: F_STEP with an optional F_CONS, or
+// -- the metrics launch, whose operand is xbar -- F_LOSS (every row of the shard: idx must be null)
+// and / or F_CONS.  CSR mixing only, no halo rows.
+struct SoftmaxArgs {
+  RoundArgs r;
+  int32_t n_classes;  // 2 <= C <= 16
+};
+constexpr int kSoftmaxMaxClasses = 16;
+constexpr int64_t kSoftmaxMaxLd = 1024;  // padded row length the register / LDS budget holds (every dtype pair)
+// per element-type pair (softmax_f32.hip / softmax_f64.hip / softmax_x32.hip)
+hipError_t launch_softmax_f32(const SoftmaxArgs& a, int n_workers, hipStream_t s);
+hipError_t launch_softmax_f64(const SoftmaxArgs& a, int n_workers, hipStream_t s);
+hipError_t launch_softmax_x32(const SoftmaxArgs& a, int n_workers, hipStream_t s);
+
 // ---- large d (column-blocked): one workgroup per (worker, group of 64-chunk column blocks)
 constexpr int kSplitMaxRows = 64;  // rows held in registers by a step workgroup (16 per wave)
 // Step: g_i = (1/nb) sum_k coef_k x_k + lam x_i, x_i' = mix - eta g_i (block by block); with

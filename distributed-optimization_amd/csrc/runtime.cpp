@@ -151,6 +151,9 @@ struct dopt_ctx {
   // CHOCO-SGD (dopt_run_choco): ping-pong of the public copies, [N x ld] T, allocated (zero) on first use
   void* xh[2] = {nullptr, nullptr};
   int hcur = 0;
+  // softmax regression (dopt_load_shards_softmax): classes of the context, 0 for the vector objectives.  The
+  // state rows (xs, xbar, part, S) then hold sm_C blocks of ld elements, class-major; ld / nch stay the data row's
+  int sm_C = 0;
   void* xbar[2] = {nullptr, nullptr};
   int xb = 0;  // xbar[xb] = average of the current iterates
   double* S = nullptr;             // [ld] column sums of the current iterates (complete-graph mixing)
@@ -474,16 +477,20 @@ int ensure_slabs(dopt_ctx* c, int64_t need) {
   return DOPT_OK;
 }
 
+// Elements of a state row: the padded data row, or -- softmax contexts -- one per class.
+int64_t state_ld(const dopt_ctx* c) { return c->sm_C ? c->sm_C * c->ld : c->ld; }
+
 int alloc_state(dopt_ctx* c) {
-  const size_t st = (size_t)std::max<int64_t>(1, c->n) * c->ld * c->esz;
+  const int64_t sld = state_ld(c);
+  const size_t st = (size_t)std::max<int64_t>(1, c->n) * sld * c->esz;
   int rc;
   for (int k = 0; k < 2; ++k) {
     if ((rc = dalloc(&c->xs[k], st))) return rc;
     HIPOK(hipMemsetAsync(c->xs[k], 0, st, c->stream));  // Worker.x = zeros (worker.py:13)
-    if ((rc = dalloc(&c->xg[k], c->ld * c->esz))) return rc;
-    HIPOK(hipMemsetAsync(c->xg[k], 0, c->ld * c->esz, c->stream));  // trainer.py:11
-    if ((rc = dalloc(&c->xbar[k], c->ld * c->esz))) return rc;
-    HIPOK(hipMemsetAsync(c->xbar[k], 0, c->ld * c->esz, c->stream));
+    if ((rc = dalloc(&c->xg[k], sld * c->esz))) return rc;
+    HIPOK(hipMemsetAsync(c->xg[k], 0, sld * c->esz, c->stream));  // trainer.py:11
+    if ((rc = dalloc(&c->xbar[k], sld * c->esz))) return rc;
+    HIPOK(hipMemsetAsync(c->xbar[k], 0, sld * c->esz, c->stream));
   }
   dfree(c->G);  // allocated on first centralized run
   dfree(c->ys[0]);  // new data: the tracker state of dopt_run_gt is gone
@@ -497,23 +504,37 @@ int alloc_state(dopt_ctx* c) {
   c->gcur = 0;
   c->xb = 0;
   c->groups = (int)((std::max<int64_t>(1, c->n) + kRowsPerGroup - 1) / kRowsPerGroup);
-  if ((rc = dalloc_t(&c->part, (size_t)c->groups * c->ld * sizeof(double)))) return rc;
+  if ((rc = dalloc_t(&c->part, (size_t)c->groups * sld * sizeof(double)))) return rc;
   if ((rc = make_chunks(c, c->rows, &c->choff, &c->n_chunks))) return rc;
   c->slab_cap = 0;
   if ((rc = ensure_slabs(c, std::max(c->n, c->n_chunks)))) return rc;
-  if ((rc = dalloc_t(&c->S, (size_t)c->ld * sizeof(double)))) return rc;
-  HIPOK(hipMemsetAsync(c->S, 0, (size_t)c->ld * sizeof(double), c->stream));
-  if ((rc = dalloc(&c->S_t, (size_t)c->ld * c->esz))) return rc;
+  if ((rc = dalloc_t(&c->S, (size_t)sld * sizeof(double)))) return rc;
+  HIPOK(hipMemsetAsync(c->S, 0, (size_t)sld * sizeof(double), c->stream));
+  if ((rc = dalloc(&c->S_t, (size_t)sld * c->esz))) return rc;
   HIPOK(hipStreamSynchronize(c->stream));
   return DOPT_OK;
 }
 
-int set_layout(dopt_ctx* c, int problem, int64_t n, int64_t d) {
+// n_classes > 0: a softmax context (dopt_load_shards_softmax), else one of the vector objectives.
+int set_layout(dopt_ctx* c, int problem, int64_t n, int64_t d, int64_t n_classes = 0) {
   c->carry_pending = false;
   c->rs_live = c->rs_gram_ok = false;  // new data: the row-space state and the Gram matrices are gone
   c->rs_wg = 0;
-  if (problem != DOPT_LOGISTIC && problem != DOPT_QUADRATIC)
+  c->sm_C = 0;
+  if (problem == DOPT_SOFTMAX && n_classes == 0)
+    return fail(DOPT_ERR_UNSUPPORTED, "softmax shards are loaded by dopt_load_shards_softmax (there is no softmax "
+                "generator)");
+  if (problem != DOPT_LOGISTIC && problem != DOPT_QUADRATIC && problem != DOPT_SOFTMAX)
     return fail(DOPT_ERR_UNSUPPORTED, "unknown problem %d", problem);
+  if (problem == DOPT_SOFTMAX) {
+    if (n_classes < 2 || n_classes > kSoftmaxMaxClasses)
+      return fail(DOPT_ERR_UNSUPPORTED, "softmax: %lld classes; the round kernel pads the classes to one matrix tile "
+                  "(2 <= n_classes <= %d)", (long long)n_classes, kSoftmaxMaxClasses);
+    if (d >= 1 && (d + c->vn - 1) / c->vn * c->vn > kSoftmaxMaxLd)
+      return fail(DOPT_ERR_UNSUPPORTED, "softmax: rows of %lld elements; the round kernel keeps a worker's C x d "
+                  "operands and accumulators in registers (padded rows of at most %lld elements)", (long long)d,
+                  (long long)kSoftmaxMaxLd);
+  }
   CHECK_ARG(n >= 1 && d >= 1, "n_workers (%lld) and d (%lld) must be >= 1", (long long)n, (long long)d);
   CHECK_ARG(n < (1LL << 31), "n_workers too large");
   const int64_t ld = (d + c->vn - 1) / c->vn * c->vn;
@@ -537,7 +558,8 @@ int set_layout(dopt_ctx* c, int problem, int64_t n, int64_t d) {
   c->tiled = c->split;
   c->ldx = c->tiled ? (nch + kTileRowChunks - 1) / kTileRowChunks * kTileRowChunks * c->vn : ld;
   c->cpl = cpl;
-  c->nchs = ld * (int64_t)c->esz / 16;
+  c->sm_C = problem == DOPT_SOFTMAX ? (int)n_classes : 0;
+  c->nchs = state_ld(c) * (int64_t)c->esz / 16;
   c->cpls = cpl_for(c->nchs);
   c->have_topo = false;
   c->obj_sep = false;
@@ -656,7 +678,7 @@ void finalize_metrics(const double* raw, int64_t T, int problem, int64_t n, int6
     if (obj_out) {
       double obj = 0.0;  // empty data -> 0.0, no regulariser (obj_problems.py:4,40)
       if (m_obj > 0) {
-        const double data = (problem == DOPT_LOGISTIC) ? r[1] / (double)m_obj : 0.5 * (r[1] / (double)m_obj);
+        const double data = (problem == DOPT_LOGISTIC || problem == DOPT_SOFTMAX) ? r[1] / (double)m_obj : 0.5 * (r[1] / (double)m_obj);
         obj = data + (lam_obj / 2.0) * r[2];
       }
       obj_out[h] = obj - f_opt;
@@ -1259,6 +1281,12 @@ bool split_few_metrics(dopt_ctx* c) {
   return c->n < 256 && c->problem == DOPT_LOGISTIC && !c->split && !c->obj_sep;
 }
 
+// Every gradient / objective entry point of the vector objectives refuses a softmax context.
+int no_softmax(const char* fn) {
+  return fail(DOPT_ERR_UNSUPPORTED, "%s: not available on a softmax context (dopt_load_shards_softmax); its rounds "
+              "are dopt_run_softmax, its iterates dopt_softmax_set_models / dopt_softmax_get_models", fn);
+}
+
 int check_run(dopt_ctx* c, int64_t T, int64_t batch, const int32_t* idx, bool need_topo) {
   if (!c->have_data) return fail(DOPT_ERR_STATE, "no shards loaded");
   if (need_topo && !c->have_topo) return fail(DOPT_ERR_STATE, "no topology set");
@@ -1396,14 +1424,14 @@ int dopt_destroy(dopt_ctx* c) {
   return DOPT_OK;
 }
 
-int dopt_load_shards(dopt_ctx* c, int problem, int64_t n_workers, int64_t d, const int64_t* off,
-                     const void* X, const void* y, int src_f32) {
+static int load_shards(dopt_ctx* c, int problem, int64_t n_workers, int64_t d, const int64_t* off, const void* X,
+                       const void* y, int src_f32, int64_t n_classes) {
   CHECK_ARG(c, "ctx is NULL");
   CHECK_ARG(off, "shard_offsets is NULL");
   int rc;
   if ((rc = set_device(c))) return rc;
   c->have_data = false;
-  if ((rc = set_layout(c, problem, n_workers, d))) return rc;
+  if ((rc = set_layout(c, problem, n_workers, d, n_classes))) return rc;
   CHECK_ARG(off[0] == 0, "shard_offsets[0] must be 0");
   int64_t max_m = 0, min_m = n_workers > 0 ? off[1] - off[0] : 0;
   for (int64_t i = 0; i < n_workers; ++i) {
@@ -1413,6 +1441,11 @@ int dopt_load_shards(dopt_ctx* c, int problem, int64_t n_workers, int64_t d, con
   }
   const int64_t rows = off[n_workers];
   CHECK_ARG(rows == 0 || (X && y), "X / y are NULL");
+  for (int64_t k = 0; k < rows && n_classes > 0; ++k) {  // softmax labels: integers in [0, C)
+    const double v = src_f32 ? (double)((const float*)y)[k] : ((const double*)y)[k];
+    CHECK_ARG(v >= 0.0 && v < (double)n_classes && v == (double)(int64_t)v,
+              "label %g of row %lld is not an integer in [0, %lld)", v, (long long)k, (long long)n_classes);
+  }
   c->rows = rows;
   c->max_m = max_m;
   c->min_m = min_m;
@@ -1426,6 +1459,17 @@ int dopt_load_shards(dopt_ctx* c, int problem, int64_t n_workers, int64_t d, con
   if ((rc = alloc_state(c))) return rc;
   c->have_data = true;
   return DOPT_OK;
+}
+
+int dopt_load_shards(dopt_ctx* c, int problem, int64_t n_workers, int64_t d, const int64_t* off,
+                     const void* X, const void* y, int src_f32) {
+  return load_shards(c, problem, n_workers, d, off, X, y, src_f32, 0);
+}
+
+int dopt_load_shards_softmax(dopt_ctx* c, int64_t n_workers, int64_t d, int64_t n_classes, const int64_t* off,
+                             const void* X, const void* y, int src_f32) {
+  CHECK_ARG(n_classes >= 1, "n_classes must be >= 1");
+  return load_shards(c, DOPT_SOFTMAX, n_workers, d, off, X, y, src_f32, n_classes);
 }
 
 int dopt_generate_shards(dopt_ctx* c, int problem, int64_t n_workers, int64_t d, int64_t rpw,
@@ -1461,6 +1505,7 @@ int dopt_generate_shards(dopt_ctx* c, int problem, int64_t n_workers, int64_t d,
 }
 
 int dopt_load_objective_data(dopt_ctx* c, int64_t n_rows, const void* X, const void* y, int src_f32) {
+  if (c && c->sm_C) return no_softmax(__func__);
   CHECK_ARG(c, "ctx is NULL");
   if (!c->have_data) return fail(DOPT_ERR_STATE, "load the shards first");
   CHECK_ARG(n_rows >= 0, "n_rows must be >= 0");
@@ -1567,6 +1612,7 @@ int dopt_set_topology(dopt_ctx* c, int64_t n_workers, const int64_t* row_ptr, co
 }
 
 int dopt_set_mixing_mean(dopt_ctx* c, int64_t n_workers, double w_off, const double* w_diag) {
+  if (c && c->sm_C) return no_softmax(__func__);
   CHECK_ARG(c && w_diag, "NULL argument");
   if (!c->have_data) return fail(DOPT_ERR_STATE, "load the shards first");
   CHECK_ARG(n_workers == c->n, "mixing has %lld workers, data has %lld", (long long)n_workers, (long long)c->n);
@@ -1596,6 +1642,7 @@ int dopt_set_mixing_mean(dopt_ctx* c, int64_t n_workers, double w_off, const dou
 }
 
 int dopt_set_models(dopt_ctx* c, const double* x) {
+  if (c && c->sm_C) return no_softmax(__func__);
   if (c) c->send_fresh = c->carry_pending = c->rs_live = false;
   CHECK_ARG(c && x, "NULL argument");
   if (!c->have_data) return fail(DOPT_ERR_STATE, "load the shards first");
@@ -1610,11 +1657,12 @@ int dopt_zero_models(dopt_ctx* c) {
   if (!c->have_data) return fail(DOPT_ERR_STATE, "load the shards first");
   int rc;
   if ((rc = set_device(c))) return rc;
-  HIPOK(hipMemsetAsync(c->xs[c->cur], 0, (size_t)c->n * c->ld * c->esz, c->stream));  // worker.py:13
+  HIPOK(hipMemsetAsync(c->xs[c->cur], 0, (size_t)c->n * state_ld(c) * c->esz, c->stream));  // worker.py:13
   return DOPT_OK;
 }
 
 int dopt_get_models(dopt_ctx* c, double* x) {
+  if (c && c->sm_C) return no_softmax(__func__);
   CHECK_ARG(c && x, "NULL argument");
   if (!c->have_data) return fail(DOPT_ERR_STATE, "load the shards first");
   int rc;
@@ -1624,6 +1672,7 @@ int dopt_get_models(dopt_ctx* c, double* x) {
 }
 
 int dopt_set_global(dopt_ctx* c, const double* x) {
+  if (c && c->sm_C) return no_softmax(__func__);
   CHECK_ARG(c && x, "NULL argument");
   if (!c->have_data) return fail(DOPT_ERR_STATE, "load the shards first");
   int rc;
@@ -1632,6 +1681,7 @@ int dopt_set_global(dopt_ctx* c, const double* x) {
 }
 
 int dopt_get_global(dopt_ctx* c, double* x) {
+  if (c && c->sm_C) return no_softmax(__func__);
   CHECK_ARG(c && x, "NULL argument");
   if (!c->have_data) return fail(DOPT_ERR_STATE, "load the shards first");
   int rc;
@@ -1776,6 +1826,7 @@ static int run_dsgd(dopt_ctx* c, int64_t t0, int64_t T, double eta0, int64_t bat
 int dopt_run_dsgd(dopt_ctx* c, int64_t t0, int64_t T, double eta0, int64_t batch, const int32_t* idx,
                   double lam_grad, double lam_obj, double f_opt, uint32_t flags, double* obj_out,
                   double* cons_out, double* time_out) {
+  if (c && c->sm_C) return no_softmax(__func__);
   return run_dsgd(c, t0, T, eta0, batch, idx, lam_grad, lam_obj, f_opt, flags, obj_out, cons_out, time_out, false,
                   nullptr);
 }
@@ -1783,6 +1834,7 @@ int dopt_run_dsgd(dopt_ctx* c, int64_t t0, int64_t T, double eta0, int64_t batch
 int dopt_run_dsgd_pipelined(dopt_ctx* c, int64_t t0, int64_t T, double eta0, int64_t batch, const int32_t* idx,
                             double lam_grad, double lam_obj, double f_opt, uint32_t flags, double* obj_out,
                             double* cons_out, double* time_out, int64_t* n_out) {
+  if (c && c->sm_C) return no_softmax(__func__);
   CHECK_ARG(n_out, "n_out is NULL");
   return run_dsgd(c, t0, T, eta0, batch, idx, lam_grad, lam_obj, f_opt, flags, obj_out, cons_out, time_out, true,
                   n_out);
@@ -1791,6 +1843,7 @@ int dopt_run_dsgd_pipelined(dopt_ctx* c, int64_t t0, int64_t T, double eta0, int
 int dopt_run_centralized(dopt_ctx* c, int64_t t0, int64_t T, double eta0, int64_t batch,
                          const int32_t* idx, double lam_grad, double lam_obj, double f_opt,
                          uint32_t flags, double* obj_out, double* time_out) {
+  if (c && c->sm_C) return no_softmax(__func__);
   CHECK_ARG(c, "ctx is NULL");
   c->carry_pending = false;
   int rc;
@@ -1976,10 +2029,12 @@ int run_gt(dopt_ctx* c, int64_t t0, int64_t T, double eta0, int64_t batch, const
 int dopt_run_gt(dopt_ctx* c, int64_t t0, int64_t T, double eta0, int64_t batch, const int32_t* idx, double lam_grad,
                 double lam_obj, double f_opt, uint32_t flags, double* obj_out, double* cons_out,
                 double* time_out) {
+  if (c && c->sm_C) return no_softmax(__func__);
   return run_gt(c, t0, T, eta0, batch, idx, lam_grad, lam_obj, f_opt, flags, obj_out, cons_out, time_out);
 }
 
 int dopt_gt_set_state(dopt_ctx* c, const double* y, const double* g) {
+  if (c && c->sm_C) return no_softmax(__func__);
   CHECK_ARG(c, "ctx is NULL");
   int rc;
   if ((rc = check_gt(c))) return rc;
@@ -2001,6 +2056,7 @@ int dopt_gt_set_state(dopt_ctx* c, const double* y, const double* g) {
 }
 
 int dopt_gt_get_state(dopt_ctx* c, double* y, double* g) {
+  if (c && c->sm_C) return no_softmax(__func__);
   CHECK_ARG(c, "ctx is NULL");
   int rc;
   if ((rc = check_gt(c))) return rc;
@@ -2147,11 +2203,13 @@ int run_choco(dopt_ctx* c, int64_t t0, int64_t T, double eta0, int64_t batch, co
 int dopt_run_choco(dopt_ctx* c, int64_t t0, int64_t T, double eta0, int64_t batch, const int32_t* idx,
                    double lam_grad, double lam_obj, double f_opt, uint32_t flags, int64_t k, double gamma,
                    double* obj_out, double* cons_out, double* time_out) {
+  if (c && c->sm_C) return no_softmax(__func__);
   return run_choco(c, t0, T, eta0, batch, idx, lam_grad, lam_obj, f_opt, flags, k, gamma, obj_out, cons_out,
                    time_out);
 }
 
 int dopt_choco_set_state(dopt_ctx* c, const double* xhat) {
+  if (c && c->sm_C) return no_softmax(__func__);
   CHECK_ARG(c, "ctx is NULL");
   int rc;
   if ((rc = check_choco(c))) return rc;
@@ -2167,6 +2225,7 @@ int dopt_choco_set_state(dopt_ctx* c, const double* xhat) {
 }
 
 int dopt_choco_get_state(dopt_ctx* c, double* xhat) {
+  if (c && c->sm_C) return no_softmax(__func__);
   CHECK_ARG(c, "ctx is NULL");
   CHECK_ARG(xhat, "xhat is NULL");
   int rc;
@@ -2174,6 +2233,133 @@ int dopt_choco_get_state(dopt_ctx* c, double* xhat) {
   if ((rc = set_device(c))) return rc;
   if ((rc = ensure_choco(c))) return rc;
   return download_rows(c, c->dtype, c->xh[c->hcur], xhat, c->n, c->d, c->ld);
+}
+
+// ---------------------------------------------------------------------------- softmax regression
+namespace {
+
+hipError_t launch_softmax(dopt_ctx* c, const SoftmaxArgs& g) {
+  if (c->dtype == DOPT_F32) return launch_softmax_f32(g, (int)c->n, c->stream);
+  if (c->xdtype == DOPT_F32) return launch_softmax_x32(g, (int)c->n, c->stream);
+  return launch_softmax_f64(g, (int)c->n, c->stream);
+}
+
+int check_softmax(dopt_ctx* c) {
+  if (!c->have_data) return fail(DOPT_ERR_STATE, "no shards loaded");
+  if (!c->sm_C)
+    return fail(DOPT_ERR_UNSUPPORTED, "not a softmax context: load the shards with dopt_load_shards_softmax");
+  return DOPT_OK;
+}
+
+// T rounds of softmax D-SGD on run_gt's schedule: k_round_softmax, then the column sums of the new
+// iterates (over the C ld elements of a state row) with the history row of the previous round folded
+// in.  Round h's step launch takes the consensus of W_h at Wbar_h (history[h - 1]) in its epilogue; the
+// objective of that row is one more launch of the same kernel without the step, whose operand is
+// Wbar_h, over every row of every shard -- so minibatches cost the objective nothing extra.  The row
+// of the last iterates is the same launch with the consensus added, folded by the same column-sum
+// launch as every other row: a run split into several calls computes every history entry with the
+// same code in the same order.
+int run_softmax(dopt_ctx* c, int64_t t0, int64_t T, double eta0, int64_t batch, const int32_t* idx, double lam_grad,
+                double lam_obj, double f_opt, uint32_t flags, double* obj_out, double* cons_out, double* time_out) {
+  CHECK_ARG(c, "ctx is NULL");
+  int rc;
+  if ((rc = check_softmax(c))) return rc;
+  if (!c->have_topo) return fail(DOPT_ERR_STATE, "no topology set");
+  if (c->mean_mix || c->n_halo > 0 || c->n_send > 0 || c->sptr || c->obj_sep)  // (their setters refuse the context)
+    return fail(DOPT_ERR_UNSUPPORTED, "softmax: CSR mixing on one device over the shards' own rows only");
+  if (!idx && batch < c->max_m && c->sampler == DOPT_SAMPLE_DEVICE)
+    return fail(DOPT_ERR_UNSUPPORTED, "softmax: the device sampler is not supported; pass idx");
+  if ((rc = check_run(c, T, batch, idx, true))) return rc;
+  if ((rc = set_device(c))) return rc;
+  if (T == 0) return DOPT_OK;
+  if ((rc = ensure_hist(c, T + 1))) return rc;
+  const bool want_obj = flags & DOPT_RUN_OBJECTIVE, want_cons = flags & DOPT_RUN_CONSENSUS;
+  const bool metrics = want_obj || want_cons;
+  const int64_t CH = idx ? idx_chunk_rounds(c, T, batch) : 1;
+  const int64_t sld = state_ld(c);
+  int& xb = c->xb;
+  HIPOK(launch_colsum(c->dtype, c->xs[c->cur], c->n, sld, (int32_t)c->nchs, kRowsPerGroup, c->part, nullptr, c->n,
+                      c->xbar[xb], nullptr, 0.0, 0, c->stream, c->S, nullptr));  // Wbar of the starting iterates
+  HIPOK(launch_stamp(c->stamps, c->stream));
+
+  auto sm_args = [&](int32_t kflags) {
+    SoftmaxArgs g;
+    memset(&g, 0, sizeof(g));
+    g.r = base_args(c);
+    g.r.x_old = c->xs[c->cur];
+    g.r.x_new = c->xs[c->cur ^ 1];
+    g.r.xbar = c->xbar[xb];
+    g.r.lam = lam_grad;
+    g.r.b = batch;
+    g.r.flags = kflags;
+    g.n_classes = c->sm_C;
+    if (kflags & F_LOSS) c->loss_groups = c->n;  // per-worker loss slabs
+    return g;
+  };
+  // history row `row` = the slabs of the launches at xbar[xb]
+  auto fold_args = [&](int64_t row) {
+    double* hr = c->hraw + 3 * row;
+    return FoldArgs{want_cons ? c->slab_cons : nullptr, c->n, want_obj ? c->slab_loss : nullptr, c->loss_groups,
+                    want_obj ? c->xbar[xb] : nullptr, hr, hr + 1, hr + 2};
+  };
+
+  for (int64_t h = 0; h < T; ++h) {
+    const int64_t t = t0 + h;
+    if (idx && h % CH == 0) {
+      if ((rc = upload_idx_chunk(c, idx, h, std::min(CH, T - h), batch))) return rc;
+    }
+    const bool met = metrics && h > 0;
+    if (c->prof && (rc = prof_event(c, false))) return rc;
+    if (met && want_obj) HIPOK(launch_softmax(c, sm_args(F_LOSS)));  // the objective of W_h's row, at Wbar_h
+    SoftmaxArgs g = sm_args(F_STEP | (met && want_cons ? F_CONS : 0));
+    g.r.idx = idx ? c->idx + (h % CH) * c->n * batch : nullptr;
+    g.r.eta = eta0 / sqrt((double)(t + 1));  // trainer.py:138-140
+    HIPOK(launch_softmax(c, g));
+    if (c->prof && (rc = prof_event(c, true))) return rc;
+    // Wbar_{t+1} (trainer.py:182) and the stamp of the end of round t's update; history[h - 1] rides the launch
+    const FoldArgs fold = fold_args(met ? h - 1 : 0);
+    HIPOK(launch_colsum(c->dtype, c->xs[c->cur ^ 1], c->n, sld, (int32_t)c->nchs, kRowsPerGroup, c->part,
+                        c->stamps + h + 1, c->n, c->xbar[xb ^ 1], nullptr, 0.0, 0, c->stream, c->S,
+                        met ? &fold : nullptr));
+    c->cur ^= 1;
+    xb ^= 1;
+  }
+  if (metrics) {  // the row of the last iterates; the column sums land in the spare xbar
+    HIPOK(launch_softmax(c, sm_args((want_obj ? F_LOSS : 0) | (want_cons ? F_CONS : 0))));
+    const FoldArgs fold = fold_args(T - 1);
+    HIPOK(launch_colsum(c->dtype, c->xs[c->cur], c->n, sld, (int32_t)c->nchs, kRowsPerGroup, c->part, nullptr, c->n,
+                        c->xbar[xb ^ 1], nullptr, 0.0, 0, c->stream, c->S, &fold));
+  }
+  return finish_run(c, T, T, lam_obj, f_opt, want_obj ? obj_out : nullptr, want_cons ? cons_out : nullptr,
+                    time_out);
+}
+
+}  // namespace
+
+int dopt_run_softmax(dopt_ctx* c, int64_t t0, int64_t T, double eta0, int64_t batch, const int32_t* idx,
+                     double lam_grad, double lam_obj, double f_opt, uint32_t flags, double* obj_out, double* cons_out,
+                     double* time_out) {
+  return run_softmax(c, t0, T, eta0, batch, idx, lam_grad, lam_obj, f_opt, flags, obj_out, cons_out, time_out);
+}
+
+// The iterates as (n C) rows of d elements with the data row's stride: the class-major state row.
+int dopt_softmax_set_models(dopt_ctx* c, const double* x) {
+  CHECK_ARG(c, "ctx is NULL");
+  int rc;
+  if ((rc = check_softmax(c))) return rc;
+  if ((rc = set_device(c))) return rc;
+  if (x) return upload_rows(c, c->dtype, x, 0, c->xs[c->cur], c->n * c->sm_C, c->d, c->ld);
+  HIPOK(hipMemsetAsync(c->xs[c->cur], 0, (size_t)c->n * state_ld(c) * c->esz, c->stream));
+  HIPOK(hipStreamSynchronize(c->stream));
+  return DOPT_OK;
+}
+
+int dopt_softmax_get_models(dopt_ctx* c, double* x) {
+  CHECK_ARG(c && x, "NULL argument");
+  int rc;
+  if ((rc = check_softmax(c))) return rc;
+  if ((rc = set_device(c))) return rc;
+  return download_rows(c, c->dtype, c->xs[c->cur], x, c->n * c->sm_C, c->d, c->ld);
 }
 
 // ---------------------------------------------------------------------------- single evaluations
@@ -2303,6 +2489,7 @@ int dopt_eval_objective(dopt_ctx* c, int problem, int64_t n, int64_t d, const do
 }
 
 int dopt_eval_full(dopt_ctx* c, const double* w, double reg, double* f_out, double* g_out) {
+  if (c && c->sm_C) return no_softmax(__func__);
   CHECK_ARG(c && w && f_out, "NULL argument");
   if (!c->have_data) return fail(DOPT_ERR_STATE, "no shards loaded");
   int rc;
@@ -2370,6 +2557,7 @@ int dopt_set_sampler(dopt_ctx* c, int mode, uint64_t seed, int64_t first_worker)
 }
 
 int dopt_phase_set_round(dopt_ctx* c, int64_t t) {
+  if (c && c->sm_C) return no_softmax(__func__);
   CHECK_ARG(c, "ctx is NULL");
   CHECK_ARG(t >= 0, "round must be >= 0");
   c->ph_round = t;
@@ -2377,6 +2565,7 @@ int dopt_phase_set_round(dopt_ctx* c, int64_t t) {
 }
 
 int dopt_phase_set_step(dopt_ctx* c, int64_t t, double eta0) {
+  if (c && c->sm_C) return no_softmax(__func__);
   CHECK_ARG(c, "ctx is NULL");
   CHECK_ARG(t >= 0, "round must be >= 0");
   c->ph_round = t;
@@ -2427,6 +2616,7 @@ int dopt_get_layout(dopt_ctx* c, int64_t* ld, int64_t* elem_bytes) {
 }
 
 int dopt_set_partition(dopt_ctx* c, int64_t n_global, int64_t rows_global) {
+  if (c && c->sm_C) return no_softmax(__func__);
   CHECK_ARG(c, "ctx is NULL");
   if (!c->have_data) return fail(DOPT_ERR_STATE, "load the shards first");
   CHECK_ARG(n_global >= c->n && rows_global >= 0, "global sizes smaller than the local slice");
@@ -2439,6 +2629,7 @@ int dopt_set_partition(dopt_ctx* c, int64_t n_global, int64_t rows_global) {
 
 int dopt_set_halo(dopt_ctx* c, int64_t n_halo, void* halo_dev, int64_t n_send, void* send_dev,
                   const int32_t* send_ids) {
+  if (c && c->sm_C) return no_softmax(__func__);
   CHECK_ARG(c, "ctx is NULL");
   if (!c->have_data) return fail(DOPT_ERR_STATE, "load the shards first");
   CHECK_ARG(n_halo >= 0 && n_send >= 0, "negative sizes");
@@ -2478,6 +2669,7 @@ int dopt_set_halo(dopt_ctx* c, int64_t n_halo, void* halo_dev, int64_t n_send, v
 }
 
 int dopt_phase_gather(dopt_ctx* c) {
+  if (c && c->sm_C) return no_softmax(__func__);
   CHECK_ARG(c, "ctx is NULL");
   if (!c->have_data) return fail(DOPT_ERR_STATE, "no shards loaded");
   if (c->send_fresh) return DOPT_OK;  // the last mix wrote these rows already
@@ -2489,12 +2681,14 @@ int dopt_phase_gather(dopt_ctx* c) {
 }
 
 int dopt_phase_interior_count(dopt_ctx* c, int64_t* n_interior) {
+  if (c && c->sm_C) return no_softmax(__func__);
   CHECK_ARG(c && n_interior, "NULL argument");
   *n_interior = c->have_topo && !c->mean_mix && c->interior ? c->n_interior : 0;
   return DOPT_OK;
 }
 
 int dopt_phase_chain(dopt_ctx* c, int mark, int* was_pending) {
+  if (c && c->sm_C) return no_softmax(__func__);
   CHECK_ARG(c && was_pending, "NULL argument");
   *was_pending = c->carry_pending ? 1 : 0;
   c->carry_pending = mark != 0;
@@ -2503,6 +2697,7 @@ int dopt_phase_chain(dopt_ctx* c, int mark, int* was_pending) {
 }
 
 int dopt_phase_begin(dopt_ctx* c, int64_t batch) {
+  if (c && c->sm_C) return no_softmax(__func__);
   CHECK_ARG(c, "ctx is NULL");
   c->carry_pending = false;
   if (!c->have_data) return fail(DOPT_ERR_STATE, "no shards loaded");
@@ -2524,6 +2719,7 @@ int dopt_phase_begin(dopt_ctx* c, int64_t batch) {
 }
 
 int dopt_phase_grad(dopt_ctx* c, int64_t batch, const int32_t* idx, double lam_grad, uint32_t metric_flags) {
+  if (c && c->sm_C) return no_softmax(__func__);
   CHECK_ARG(c, "ctx is NULL");
   int rc;
   if ((rc = check_run(c, 1, batch, idx, false))) return rc;
@@ -2583,6 +2779,7 @@ int dopt_phase_grad(dopt_ctx* c, int64_t batch, const int32_t* idx, double lam_g
 }
 
 int dopt_phase_mix(dopt_ctx* c, int64_t t, double eta0) {
+  if (c && c->sm_C) return no_softmax(__func__);
   CHECK_ARG(c, "ctx is NULL");
   if (!c->have_topo || !c->G) return fail(DOPT_ERR_STATE, "topology / gradient phase missing");
   RoundArgs a = base_args(c);
@@ -2629,6 +2826,7 @@ int dopt_phase_mix(dopt_ctx* c, int64_t t, double eta0) {
 // ---- centralized trainer across ranks (trainer.py:41-71): per-rank gradients at the
 // shared iterate, all-reduced column sums of the gradients, the step.
 int dopt_phase_grad_shared(dopt_ctx* c, int64_t batch, const int32_t* idx, double lam_grad, int fuse_loss) {
+  if (c && c->sm_C) return no_softmax(__func__);
   CHECK_ARG(c, "ctx is NULL");
   int rc;
   if ((rc = check_run(c, 1, batch, idx, false))) return rc;
@@ -2661,6 +2859,7 @@ int dopt_phase_grad_shared(dopt_ctx* c, int64_t batch, const int32_t* idx, doubl
 }
 
 int dopt_phase_colsum_grad(dopt_ctx* c, double* sum_dev) {
+  if (c && c->sm_C) return no_softmax(__func__);
   CHECK_ARG(c && sum_dev, "NULL argument");
   if (!c->G) return fail(DOPT_ERR_STATE, "no gradient phase yet");
   HIPOK(launch_colsum_partial(c->dtype, c->G, c->n, c->ld, (int32_t)c->nchs, kRowsPerGroup, c->part, nullptr,
@@ -2671,6 +2870,7 @@ int dopt_phase_colsum_grad(dopt_ctx* c, double* sum_dev) {
 }
 
 int dopt_phase_central_step(dopt_ctx* c, const double* sum_dev, int64_t t, double eta0) {
+  if (c && c->sm_C) return no_softmax(__func__);
   CHECK_ARG(c && sum_dev, "NULL argument");
   HIPOK(launch_colsum_final(c->dtype, sum_dev, 1, n_div(c), c->ld, (int32_t)c->nchs, c->xg[c->gcur ^ 1],
                             c->xg[c->gcur], eta0 / sqrt((double)(t + 1)), 1, c->stream));
@@ -2679,6 +2879,7 @@ int dopt_phase_central_step(dopt_ctx* c, const double* sum_dev, int64_t t, doubl
 }
 
 int dopt_phase_metrics_pass_shared(dopt_ctx* c) {
+  if (c && c->sm_C) return no_softmax(__func__);
   CHECK_ARG(c, "ctx is NULL");
   if (c->split) {
     int rc;
@@ -2689,6 +2890,7 @@ int dopt_phase_metrics_pass_shared(dopt_ctx* c) {
 }
 
 int dopt_phase_metrics_shared(dopt_ctx* c, int include_xnorm, double* out_dev) {
+  if (c && c->sm_C) return no_softmax(__func__);
   CHECK_ARG(c && out_dev, "NULL argument");
   HIPOK(launch_history(c->dtype, nullptr, c->slab_loss, c->n, c->loss_groups, c->xg[c->gcur], c->ld,
                        (int32_t)c->nchs, include_xnorm != 0, out_dev, c->stream));
@@ -2696,6 +2898,7 @@ int dopt_phase_metrics_shared(dopt_ctx* c, int include_xnorm, double* out_dev) {
 }
 
 int dopt_phase_colsum(dopt_ctx* c, double* sum_dev) {
+  if (c && c->sm_C) return no_softmax(__func__);
   CHECK_ARG(c && sum_dev, "NULL argument");
   int rc;
   if ((rc = rs_end(c))) return rc;
@@ -2707,6 +2910,7 @@ int dopt_phase_colsum(dopt_ctx* c, double* sum_dev) {
 }
 
 int dopt_phase_xbar(dopt_ctx* c, const double* sum_dev) {
+  if (c && c->sm_C) return no_softmax(__func__);
   CHECK_ARG(c && sum_dev, "NULL argument");
   HIPOK(launch_colsum_final(c->dtype, sum_dev, 1, n_div(c), c->ld, (int32_t)c->nchs, c->xbar[c->xb ^ 1], nullptr,
                             0.0, 0, c->stream));
@@ -2716,6 +2920,7 @@ int dopt_phase_xbar(dopt_ctx* c, const double* sum_dev) {
 }
 
 int dopt_phase_fold(dopt_ctx* c, double* cons_out, double* xnorm_out, double* loss_out, int slab) {
+  if (c && c->sm_C) return no_softmax(__func__);
   CHECK_ARG(c, "ctx is NULL");
   CHECK_ARG(slab == 0 || slab == 1, "slab must be 0 or 1");
   if (c->rs_live && !c->rs_sweep) {  // row-space rounds: ||xbar||^2 from the average update's block partials
@@ -2732,6 +2937,7 @@ int dopt_phase_fold(dopt_ctx* c, double* cons_out, double* xnorm_out, double* lo
 // The replicated d-vectors (xbar, Z) take the all-reduced column sums, so every rank holds
 // the same ones; the metric partials are this rank's workers' (folded by dopt_phase_fold).
 int dopt_rs_phase_begin(dopt_ctx* c, int commit, int* ok, uint64_t* hash) {
+  if (c && c->sm_C) return no_softmax(__func__);
   CHECK_ARG(c && ok && hash, "NULL argument");
   if (!c->have_data) return fail(DOPT_ERR_STATE, "no shards loaded");
   *ok = 0;
@@ -2763,6 +2969,7 @@ int dopt_rs_phase_begin(dopt_ctx* c, int commit, int* ok, uint64_t* hash) {
 
 int dopt_rs_phase_round(dopt_ctx* c, int64_t t, double eta0, double lam_grad, uint32_t metric_flags,
                         double* sum_dev) {
+  if (c && c->sm_C) return no_softmax(__func__);
   CHECK_ARG(c && sum_dev, "NULL argument");
   if (!c->rs_live) return fail(DOPT_ERR_STATE, "dopt_rs_phase_begin first");
   if (int rc = rs_sweep_closed(c)) return rc;
@@ -2786,6 +2993,7 @@ int dopt_rs_phase_round(dopt_ctx* c, int64_t t, double eta0, double lam_grad, ui
 }
 
 int dopt_rs_phase_pass(dopt_ctx* c, int32_t chunk, int32_t n_chunks, double* sum_dev, int64_t* col_range) {
+  if (c && c->sm_C) return no_softmax(__func__);
   CHECK_ARG(c && sum_dev && col_range, "NULL argument");
   if (!c->rs_live) return fail(DOPT_ERR_STATE, "dopt_rs_phase_begin first");
   CHECK_ARG(n_chunks >= 1 && chunk >= 0 && chunk < n_chunks, "chunk %d of %d", chunk, n_chunks);
@@ -2809,6 +3017,7 @@ int dopt_rs_phase_pass(dopt_ctx* c, int32_t chunk, int32_t n_chunks, double* sum
 }
 
 int dopt_rs_phase_rows(dopt_ctx* c, int64_t t, double eta0, double lam_grad, uint32_t metric_flags) {
+  if (c && c->sm_C) return no_softmax(__func__);
   CHECK_ARG(c, "ctx is NULL");
   if (!c->rs_live) return fail(DOPT_ERR_STATE, "dopt_rs_phase_begin first");
   if (int rc = rs_sweep_closed(c)) return rc;
@@ -2825,6 +3034,7 @@ int dopt_rs_phase_rows(dopt_ctx* c, int64_t t, double eta0, double lam_grad, uin
 }
 
 int dopt_rs_phase_cols(dopt_ctx* c, int64_t t, double eta0, double lam_grad, const double* sum_dev) {
+  if (c && c->sm_C) return no_softmax(__func__);
   CHECK_ARG(c && sum_dev, "NULL argument");
   if (!c->rs_live) return fail(DOPT_ERR_STATE, "dopt_rs_phase_begin first");
   if (int rc = rs_sweep_closed(c)) return rc;
@@ -2843,6 +3053,7 @@ int dopt_rs_phase_cols(dopt_ctx* c, int64_t t, double eta0, double lam_grad, con
 // the chunks of one update in any order, the last one with last = 1.
 int dopt_rs_phase_cols_range(dopt_ctx* c, int64_t t, double eta0, double lam_grad, const double* sum_dev,
                              int64_t c0, int64_t c1, int32_t last) {
+  if (c && c->sm_C) return no_softmax(__func__);
   CHECK_ARG(c && sum_dev, "NULL argument");
   if (!c->rs_live) return fail(DOPT_ERR_STATE, "dopt_rs_phase_begin first");
   const int dt = c->dtype == DOPT_F32 ? 0 : 1;
@@ -2861,6 +3072,7 @@ int dopt_rs_phase_cols_range(dopt_ctx* c, int64_t t, double eta0, double lam_gra
 }
 
 int dopt_rs_phase_metrics(dopt_ctx* c, uint32_t metric_flags) {
+  if (c && c->sm_C) return no_softmax(__func__);
   CHECK_ARG(c, "ctx is NULL");
   if (!c->rs_live) return fail(DOPT_ERR_STATE, "dopt_rs_phase_begin first");
   if (int rc = rs_sweep_closed(c)) return rc;
@@ -2877,6 +3089,7 @@ int dopt_rs_phase_metrics(dopt_ctx* c, uint32_t metric_flags) {
 }
 
 int dopt_phase_metrics_pass(dopt_ctx* c, uint32_t flags) {
+  if (c && c->sm_C) return no_softmax(__func__);
   CHECK_ARG(c, "ctx is NULL");
   if (c->split) {
     int rc;
@@ -2889,6 +3102,7 @@ int dopt_phase_metrics_pass(dopt_ctx* c, uint32_t flags) {
 }
 
 int dopt_phase_metrics(dopt_ctx* c, uint32_t flags, int include_xnorm, double* out_dev) {
+  if (c && c->sm_C) return no_softmax(__func__);
   CHECK_ARG(c && out_dev, "NULL argument");
   const bool cons = flags & DOPT_RUN_CONSENSUS, loss = flags & DOPT_RUN_OBJECTIVE;
   HIPOK(launch_history(c->dtype, cons ? c->slab_cons : nullptr, loss ? c->slab_loss : nullptr, c->n,
@@ -2906,6 +3120,7 @@ int dopt_phase_metrics(dopt_ctx* c, uint32_t flags, int include_xnorm, double* o
 // collective per round.
 int dopt_lagged_exchange_layout(dopt_ctx* c, int32_t world, int32_t rank, const int64_t* sum_send_row,
                                 const int64_t* sum_recv_row) {
+  if (c && c->sm_C) return no_softmax(__func__);
   CHECK_ARG(c && sum_send_row && sum_recv_row, "NULL argument");
   CHECK_ARG(world >= 1 && rank >= 0 && rank < world, "bad world / rank");
   CHECK_ARG(world <= 1024, "at most 1024 ranks");
@@ -3026,6 +3241,7 @@ McsArgs lagged_args(dopt_ctx* c, const double* own_in, double* own_out, double* 
 }  // namespace
 
 int dopt_lagged_begin(dopt_ctx* c, int64_t batch) {
+  if (c && c->sm_C) return no_softmax(__func__);
   CHECK_ARG(c, "ctx is NULL");
   int rc;
   if ((rc = dopt_phase_begin(c, batch))) return rc;
@@ -3135,6 +3351,7 @@ int ipc_pull(dopt_ctx* c) {
 }  // namespace
 
 int dopt_lagged_exchange_issued(dopt_ctx* c, int* ordered) {
+  if (c && c->sm_C) return no_softmax(__func__);
   CHECK_ARG(c && ordered, "NULL argument");
   *ordered = 0;
   if (!c->lg_side) return DOPT_OK;  // no side stream: the caller orders the engine stream
@@ -3145,6 +3362,7 @@ int dopt_lagged_exchange_issued(dopt_ctx* c, int* ordered) {
 }
 
 int dopt_lagged_transport(dopt_ctx* c, dopt_comm* comm, const int64_t* send_rows, const int64_t* recv_rows) {
+  if (c && c->sm_C) return no_softmax(__func__);
   CHECK_ARG(c, "ctx is NULL");
   c->xp = nullptr;
   c->xp_ops.clear();
@@ -3180,6 +3398,7 @@ int dopt_lagged_transport(dopt_ctx* c, dopt_comm* comm, const int64_t* send_rows
 }
 
 int dopt_lagged_ipc_export(dopt_ctx* c, uint8_t* mem_handle, uint8_t* event_handle, int64_t* slot_bytes) {
+  if (c && c->sm_C) return no_softmax(__func__);
   CHECK_ARG(c && mem_handle && event_handle && slot_bytes, "NULL argument");
   if (!c->have_data) return fail(DOPT_ERR_STATE, "load the shards first");
   int rc;
@@ -3215,6 +3434,7 @@ int dopt_lagged_ipc_export(dopt_ctx* c, uint8_t* mem_handle, uint8_t* event_hand
 int dopt_lagged_ipc_import(dopt_ctx* c, int32_t world, int32_t rank, const uint8_t* mem_handles,
                            const uint8_t* event_handles, const int64_t* slot_bytes, const int64_t* src_off,
                            const int64_t* recv_rows, int64_t* counters, double timeout_s) {
+  if (c && c->sm_C) return no_softmax(__func__);
   CHECK_ARG(c && mem_handles && event_handles && slot_bytes && src_off && recv_rows && counters, "NULL argument");
   CHECK_ARG(c->ipc_send, "dopt_lagged_ipc_export first");
   CHECK_ARG(c->lg_world == world && c->lg_rank == rank,
@@ -3303,6 +3523,7 @@ int dopt_lagged_ipc_import(dopt_ctx* c, int32_t world, int32_t rank, const uint8
 }
 
 int dopt_lagged_ipc_check(dopt_ctx* c, int32_t step) {
+  if (c && c->sm_C) return no_softmax(__func__);
   CHECK_ARG(c, "ctx is NULL");
   CHECK_ARG(step == 0 || step == 1, "step 0 (publish) or 1 (pull)");
   if (!c->ipc) return fail(DOPT_ERR_STATE, "no pull transport (dopt_lagged_ipc_import first)");
@@ -3314,6 +3535,7 @@ int dopt_lagged_ipc_check(dopt_ctx* c, int32_t step) {
 }
 
 int dopt_lagged_exchange(dopt_ctx* c) {
+  if (c && c->sm_C) return no_softmax(__func__);
   CHECK_ARG(c, "ctx is NULL");
   int rc;
   if (c->ipc) {
@@ -3332,6 +3554,7 @@ int dopt_lagged_exchange(dopt_ctx* c) {
 }
 
 int dopt_lagged_side_stream(dopt_ctx* c, void* stream) {
+  if (c && c->sm_C) return no_softmax(__func__);
   CHECK_ARG(c, "ctx is NULL");
   int rc;
   if ((rc = set_device(c))) return rc;
@@ -3344,6 +3567,7 @@ int dopt_lagged_side_stream(dopt_ctx* c, void* stream) {
 
 int dopt_lagged_grad(dopt_ctx* c, int64_t t, double eta0, int64_t batch, const int32_t* idx, double lam_grad,
                      uint32_t metric_flags) {
+  if (c && c->sm_C) return no_softmax(__func__);
   int rc;
   if ((rc = dopt_phase_set_step(c, t, eta0))) return rc;
   return dopt_phase_grad(c, batch, idx, lam_grad, metric_flags);
@@ -3351,6 +3575,7 @@ int dopt_lagged_grad(dopt_ctx* c, int64_t t, double eta0, int64_t batch, const i
 
 int dopt_lagged_mix(dopt_ctx* c, int64_t t, double eta0, int consensus, double* cons_out, double* xnorm_out,
                     double* loss_out) {
+  if (c && c->sm_C) return no_softmax(__func__);
   CHECK_ARG(c, "ctx is NULL");
   int rc;
   if ((rc = lagged_ready(c))) return rc;
@@ -3396,6 +3621,7 @@ int dopt_lagged_mix(dopt_ctx* c, int64_t t, double eta0, int consensus, double* 
 
 int dopt_lagged_tail(dopt_ctx* c, int consensus, int objective, double* cons1, double* xnorm1, double* loss1,
                      double* cons2, double* xnorm2, double* loss2) {
+  if (c && c->sm_C) return no_softmax(__func__);
   CHECK_ARG(c, "ctx is NULL");
   int rc;
   if ((rc = lagged_ready(c))) return rc;

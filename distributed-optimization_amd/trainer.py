@@ -36,6 +36,12 @@ Config keys beyond the reference's (all optional):
   compression_k  algorithm='choco', required: entries sent per worker and round, an int in
              [1, n_features]
   choco_gamma    algorithm='choco', required: the consensus step size, a float in (0, 1]
+  problem_type   'logistic' / 'quadratic' (the reference's), or 'softmax': multinomial logistic
+             regression with labels in {0 .. num_classes - 1} and iterates of shape
+             (num_classes, n_features); DecentralizedTrainer with algorithm='dsgd' only, one
+             matrix-core launch per round, single process, CSR mixing, no checkpoints, the
+             objective over the shards' own rows
+  num_classes    problem_type='softmax', required: an int in [2, 16]
 
 Multi-process mode: when torch.distributed is initialised with more than one rank
 (e.g. `python -m torch.distributed.run --nproc-per-node 8 main.py`), every rank
@@ -58,6 +64,7 @@ DENSE_LIMIT = 4096          # dense adj / W attributes up to this many workers
 MEAN_MIX_MIN = 128          # complete graphs from this size mix through the column sums
 ROW_RESIDENT_MAX = 2048     # longer float64 rows take the column-blocked rounds (complete graphs: the
                             # row-space rounds, DESIGN.md 6c, which mix through the column sums)
+SOFTMAX_MAX_CLASSES = 16    # the softmax round pads the classes to one 16-column matrix tile
 IDX_CHUNK_ELEMS = 1 << 24   # host index buffer per device call (64 MiB of int32)
 IDX_CHUNK_ROUNDS = 512      # rounds per device call when indices are drawn (the next chunk's draw
                             # runs on a host thread while the device runs this one)
@@ -279,14 +286,15 @@ def _engine(workers, n_features, config, lo=0, hi=None, X_full=None, y_full=None
     arrays = [a for w in workers[lo:hi] for a in (w.X_local, w.y_local)]
     dev, dtype = _device(config), config.get("dtype", "float64")
     xdt = _data_dtype(config, n_features, arrays + [X_full, y_full])
-    key = (config["problem_type"], xdt, lo, hi, _fingerprint(arrays, _sampled_key(config)))
+    n_classes = config.get("num_classes") if config["problem_type"] == "softmax" else None
+    key = (config["problem_type"], n_classes, xdt, lo, hi, _fingerprint(arrays, _sampled_key(config)))
     eng = _ENGINES.get((dev, dtype))
     if eng is None or eng.data_key != key:
         if eng is not None:
             _ENGINES.pop((dev, dtype)).close()  # free the previous data set's HBM
         eng = _dopt.Engine(dev, dtype, data_dtype=xdt)
         X, y, off = _pack(workers[lo:hi], n_features, f32=eng.data_dtype == _dopt.F32)
-        eng.load_shards(config["problem_type"], X, y, off)
+        eng.load_shards(config["problem_type"], X, y, off, n_classes=n_classes)
         eng.obj_key = None
         eng.data_key = key
         _ENGINES[(dev, dtype)] = eng
@@ -343,7 +351,7 @@ def _grad_reg(cfg, n_iterations, workers):
         lam, mu = cfg["l2_regularization_lambda"], cfg["strong_convexity_mu"]
     else:
         lam, mu = cfg.get("l2_regularization_lambda", 0.0), cfg.get("strong_convexity_mu", 0.0)
-    return lam if cfg["problem_type"] == "logistic" else mu
+    return lam if cfg["problem_type"] in ("logistic", "softmax") else mu
 
 
 def _batch_size(workers):
@@ -549,6 +557,8 @@ class CentralizedTrainer:
     def run(self, n_iterations, X_full=None, y_full=None, f_opt=0.0):
         print("\n--- Running Centralized Synchronous mini-batch SGD ---")
         start_time = time.time()
+        if self.config["problem_type"] == "softmax":
+            raise NotImplementedError("softmax regression runs decentralized (DecentralizedTrainer, algorithm='dsgd')")
         self._get_objective_func()
         reg_param = self._get_regularization_param()
         self.total_floats_transmitted = 0
@@ -672,6 +682,8 @@ class DecentralizedTrainer:
 
     def run(self, n_iterations, X_full=None, y_full=None, f_opt=0.0):
         start_time = time.time()
+        if self.config["problem_type"] == "softmax":
+            return self._run_softmax(int(n_iterations), X_full, y_full, f_opt, start_time)
         self._get_objective_func()
         reg_param = self._get_regularization_param()
         self.total_floats_transmitted = 0
@@ -830,6 +842,64 @@ class DecentralizedTrainer:
         print(f"Decentralized ({self.topology}) training finished. Time: {time.time() - start_time:.2f}s")
         final_avg_model = np.mean([worker.x for worker in self.workers], axis=0)
         return self.history, final_avg_model
+
+    def _run_softmax(self, T, X_full, y_full, f_opt, start_time):
+        """config 'problem_type' = 'softmax' with 'num_classes' = C: the rounds of Engine.run_softmax
+        (multinomial logistic regression, iterates of shape (C, d), labels in {0 .. C-1}) in D-SGD's
+        chunk loop.  Every worker sends its C x d iterate along every edge, so
+        total_floats_transmitted grows per round by sum(degrees) * d * C.  A bad num_classes and every
+        unsupported combination are refused before any device call."""
+        cfg = self.config
+        C = cfg.get("num_classes")
+        if isinstance(C, bool) or not isinstance(C, (int, np.integer)) or not 2 <= C <= SOFTMAX_MAX_CLASSES:
+            raise ValueError(f"softmax needs config 'num_classes', an int in [2, {SOFTMAX_MAX_CLASSES}]: got {C!r}")
+        C = int(C)
+        if cfg.get("algorithm", "dsgd") != "dsgd":
+            raise NotImplementedError(f"softmax regression runs algorithm='dsgd', not {cfg.get('algorithm')!r}")
+        if _dist_info(cfg) is not None:
+            raise NotImplementedError("softmax regression runs in a single process (no multi-rank job)")
+        if self._mean_mixing() and self._topo.uniform_offdiag() is not None:
+            raise NotImplementedError("softmax regression mixes through the CSR matrix: raise 'mean_mixing_min' "
+                                      "above the number of workers")
+        ck_keys = [k for k in ("checkpoint_path", "checkpoint_every", "resume_from") if cfg.get(k)]
+        if ck_keys:
+            raise NotImplementedError(f"softmax regression does not checkpoint (config {ck_keys})")
+        if cfg.get("sampling", "legacy") == "device":
+            raise NotImplementedError("softmax regression draws its minibatches on the host (sampling='legacy')")
+        want_obj = X_full is not None and y_full is not None
+        if want_obj:
+            X, y, _ = _pack(self.workers, self.n_features, f32=_all_f32(self.workers))
+            if not _same_rows(X_full, y_full, X, y):
+                raise NotImplementedError("softmax regression takes its objective over the shards' own rows: X_full "
+                                          "must be their union, in worker order")
+        self.total_floats_transmitted = 0
+        reg_param = self._get_regularization_param()
+        lam_grad = _grad_reg(cfg, T, self.workers)
+        eng = _engine(self.workers, self.n_features, cfg, X_full=X_full, y_full=y_full)
+        t = self._topo
+        eng.set_topology(t.row_ptr, t.col, t.w)
+        eng.softmax_set_models(np.stack([np.asarray(w.x, dtype=np.float64).reshape(C, self.n_features)
+                                         for w in self.workers]))
+        iteration_transmission = np.sum(self.degrees) * self.n_features * C
+        eta0 = cfg["learning_rate_eta0"]
+        loop_start = time.perf_counter()
+        with closing(_index_chunks(self.workers, T, cfg)) as chunks:
+            for t0, n, b, idx, _ in chunks:
+                t_host = time.time() - start_time
+                obj, cons, tim = eng.run_softmax(n, eta0, b, lam_grad, reg_param, f_opt, idx=idx, t0=t0,
+                                                 objective=want_obj, consensus=True, want_time=True)
+                self.history["consensus_error"].extend(list(cons))
+                if want_obj:
+                    self.history["objective"].extend(list(obj))
+                self.history["time"].extend((tim + t_host).tolist())
+                self.total_floats_transmitted += n * iteration_transmission
+        self.loop_seconds = time.perf_counter() - loop_start
+        models = eng.softmax_get_models()
+        for i, worker in enumerate(self.workers):
+            worker.x = models[i]
+        _warn_nonfinite(self.history, self.config)
+        print(f"Decentralized ({self.topology}) training finished. Time: {time.time() - start_time:.2f}s")
+        return self.history, np.mean(models, axis=0)
 
     def _mean_mixing(self):
         """Complete graphs mix through the column sums from MEAN_MIX_MIN workers on, and at any

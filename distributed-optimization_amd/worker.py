@@ -11,7 +11,7 @@ single-worker API.
 import numpy as np
 
 import _dopt
-from obj_problems import logistic_stochastic_gradient, quadratic_stochastic_gradient
+from obj_problems import logistic_stochastic_gradient, quadratic_stochastic_gradient, softmax_gradient
 
 
 class Worker:
@@ -24,6 +24,8 @@ class Worker:
         self.config = config
         self.n_features = n_features
         self.x = np.zeros(n_features)
+        if config.get("problem_type") == "softmax":  # a matrix iterate: one row per class
+            self.x = np.zeros((int(config["num_classes"]), n_features))
 
     def get_mini_batch(self):
         if self.n_local_samples == 0:  # worker.py:17-18
@@ -46,4 +48,6 @@ class Worker:
             return logistic_stochastic_gradient(params, X_batch, y_batch, lambda_reg)
         elif problem == "quadratic":
             return quadratic_stochastic_gradient(params, X_batch, y_batch, mu_reg)
+        elif problem == "softmax":
+            return softmax_gradient(params, X_batch, y_batch, lambda_reg)
         raise NotImplementedError(f"Wrong {problem}")

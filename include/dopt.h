@@ -58,7 +58,8 @@ extern "C" {
  *      kernel of the engine's reading the peers' send slots through IPC handles, no RCCL kernel.
  *      Added under 9 (additions only, nothing changed): gradient tracking -- dopt_run_gt,
  *      dopt_gt_set_state, dopt_gt_get_state; CHOCO-SGD -- dopt_run_choco, dopt_choco_set_state,
- *      dopt_choco_get_state. */
+ *      dopt_choco_get_state; softmax regression -- DOPT_SOFTMAX, dopt_load_shards_softmax,
+ *      dopt_run_softmax, dopt_softmax_set_models, dopt_softmax_get_models. */
 #define DOPT_ABI_VERSION 9
 
 typedef struct dopt_ctx dopt_ctx;
@@ -77,6 +78,8 @@ typedef struct dopt_comm dopt_comm; /* an RCCL communicator the engine drives it
 /* problems: obj_problems.py:3-20 (logistic), obj_problems.py:39-53 (quadratic) */
 #define DOPT_LOGISTIC 0
 #define DOPT_QUADRATIC 1
+/* multinomial logistic (softmax) regression: contexts made by dopt_load_shards_softmax only */
+#define DOPT_SOFTMAX 2
 
 /* compute dtypes (the reference computes in float64) */
 #define DOPT_F32 0
@@ -253,6 +256,40 @@ int dopt_run_gt(dopt_ctx *ctx, int64_t t0, int64_t T, double eta0, int64_t batch
                 const int32_t *idx, double lam_grad, double lam_obj, double f_opt,
                 uint32_t flags, double *obj_out, double *cons_out, double *time_out);
 
+/* Softmax (multinomial logistic) regression over C classes -- the reference has no such
+ * objective; it is the logistic path's round (trainer.py:161-193) with a matrix iterate W_i (C x d):
+ *   z_k = W_i x_k,  p_k = softmax(z_k),  loss_k = logsumexp(z_k) - z_k[y_k]   (max-subtracted)
+ *   G_i = (1/b) sum_k (p_k - e_{y_k}) x_k^T + lam_grad W_i                   (0 for an empty shard)
+ *   W_i' = sum_j Wmix_ij W_j - eta_t G_i,   eta_t = eta0 / sqrt(t + 1)
+ *   objective = (1/m) sum_k loss_k(Wbar) + (lam_obj / 2) ||Wbar||_F^2 - f_opt,
+ *   consensus = mean_i ||W_i - Wbar||_F^2.
+ * dopt_load_shards_softmax loads the shards as dopt_load_shards does (same row layout) with labels
+ * y in {0 .. n_classes - 1} (integers, checked on the host; stored in the rows' element type, which
+ * holds them exactly) and makes the context a SOFTMAX context: its state rows are n_classes blocks of
+ * the padded row length, class-major, all zero.  2 <= n_classes <= 16; the padded row holds at most
+ * 1024 elements in every dtype pair (DOPT_ERR_UNSUPPORTED beyond).  On such a context only
+ * dopt_run_softmax computes gradients or objectives: dopt_run_dsgd*, _gt, _choco, _centralized, the
+ * phase / row-space / lagged calls, dopt_eval_full, the model and global-iterate accessors of the
+ * vector objectives, mean mixing, halo plans, partitions and a separate objective dataset return
+ * DOPT_ERR_UNSUPPORTED; dopt_generate_shards has no softmax generator.  Loading or generating
+ * shards of another problem makes it an ordinary context again. */
+int dopt_load_shards_softmax(dopt_ctx *ctx, int64_t n_workers, int64_t d, int64_t n_classes,
+                             const int64_t *shard_offsets, const void *X, const void *y, int src_f32);
+
+/* T rounds of softmax D-SGD, rounds t0..t0+T-1; parameters, outputs and schedule as dopt_run_gt:
+ * one launch of the matrix-core round kernel per round, the column sums of the new iterates with
+ * the history row of the previous round folded in, and -- DOPT_RUN_OBJECTIVE -- one metrics
+ * launch of the same kernel at Wbar per history row (every row of every shard, whatever the batch).
+ * A run split into several calls gives the bits of one call.  CSR mixing (dopt_set_topology) only;
+ * idx == NULL needs full-shard batches (no device sampler). */
+int dopt_run_softmax(dopt_ctx *ctx, int64_t t0, int64_t T, double eta0, int64_t batch,
+                     const int32_t *idx, double lam_grad, double lam_obj, double f_opt,
+                     uint32_t flags, double *obj_out, double *cons_out, double *time_out);
+
+/* Iterates of a softmax context, N x C x d row-major float64 at the boundary (NULL x: zeros). */
+int dopt_softmax_set_models(dopt_ctx *ctx, const double *x);
+int dopt_softmax_get_models(dopt_ctx *ctx, double *x);
+
 /* Tracker state of dopt_run_gt, N x d row-major float64 at the boundary like the iterates:
  * y = the trackers, g = every worker's last stochastic gradient.  A NULL argument of
  * dopt_gt_set_state sets that array to zero (NULL, NULL: a fresh chain); a NULL argument of
@@ -309,7 +346,7 @@ int dopt_eval_objective(dopt_ctx *ctx, int problem, int64_t n, int64_t d,
 
 int dopt_sync(dopt_ctx *ctx);
 /* Host: raw[T x 3] (summed over ranks) -> history values, the exact formula
- * the single-GPU path applies. */
+ * the single-GPU path applies (DOPT_SOFTMAX: the logistic formula). */
 int dopt_finalize_metrics(int problem, int64_t T, const double *raw, int64_t n_workers,
                           int64_t m_obj, double lam_obj, double f_opt, double *obj_out,
                           double *cons_out);
