@@ -74,6 +74,8 @@ _SIGS = {
     "dopt_run_softmax": ([_P, _I64, _I64, _D, _I64, _P, _D, _D, _D, ctypes.c_uint32, _P, _P, _P], ctypes.c_int),
     "dopt_softmax_set_models": ([_P, _P], ctypes.c_int),
     "dopt_softmax_get_models": ([_P, _P], ctypes.c_int),
+    "dopt_load_shards_csr": ([_P, ctypes.c_int, _I64, _I64, _P, _P, _P, _P, _P, ctypes.c_int], ctypes.c_int),
+    "dopt_run_sparse": ([_P, _I64, _I64, _D, _I64, _P, _D, _D, _D, ctypes.c_uint32, _P, _P, _P], ctypes.c_int),
     "dopt_run_centralized": ([_P, _I64, _I64, _D, _I64, _P, _D, _D, _D, ctypes.c_uint32, _P, _P], ctypes.c_int),
     "dopt_eval_gradient": ([_P, ctypes.c_int, _I64, _I64, _P, _P, _P, _D, _P], ctypes.c_int),
     "dopt_eval_objective": ([_P, ctypes.c_int, _I64, _I64, _P, _P, _P, _D, _P], ctypes.c_int),
@@ -366,6 +368,24 @@ class Engine:
         self.n, self.d, self.problem = n, d, problem
         self.shard_rows = np.diff(off)
 
+    def load_shards_csr(self, problem, indptr, indices, data, y, shard_offsets, d):
+        """dopt_load_shards_csr: shards in CSR over the global rows (scipy's indptr / indices / data with sorted
+        indices), d features.  Makes the context a sparse context: run_sparse is its round."""
+        data = np.ascontiguousarray(data)
+        src_f32 = 1 if data.dtype == np.float32 else 0
+        data = np.ascontiguousarray(data, dtype=np.float32 if src_f32 else np.float64)
+        y = np.ascontiguousarray(y, dtype=data.dtype)
+        rp = np.ascontiguousarray(indptr, dtype=np.int64)
+        col = np.ascontiguousarray(indices, dtype=np.int32)
+        off = np.ascontiguousarray(shard_offsets, dtype=np.int64)
+        if len(rp) != int(off[-1]) + 1 or len(y) != int(off[-1]) or len(col) != len(data) or len(col) != int(rp[-1]):
+            raise ValueError("load_shards_csr: indptr / indices / data / y do not describe shard_offsets[-1] rows")
+        n = len(off) - 1
+        check(lib().dopt_load_shards_csr(self._h, PROBLEMS[problem], n, int(d), _ptr(off), _ptr(rp), _ptr(col),
+                                         _ptr(data), _ptr(y), src_f32))
+        self.n, self.d, self.problem = n, int(d), problem
+        self.shard_rows = np.diff(off)
+
     def generate_shards(self, problem, n_workers, d, rows_per_worker, seed=0, flip=0.05, noise=10.0,
                         first_worker=0):
         check(lib().dopt_generate_shards(self._h, PROBLEMS[problem], int(n_workers), int(d),
@@ -468,6 +488,21 @@ class Engine:
         flags = (RUN_OBJECTIVE if objective else 0) | (RUN_CONSENSUS if consensus else 0)
         check(lib().dopt_run_gt(self._h, int(t0), T, float(eta0), int(batch), _ptr(idx), float(lam_grad),
                                 float(lam_obj), float(f_opt), flags, _ptr(obj), _ptr(cons), _ptr(tim)))
+        return obj, cons, tim
+
+    def run_sparse(self, T, eta0, batch, lam_grad, lam_obj, f_opt=0.0, idx=None, t0=0,
+                   objective=True, consensus=True, want_time=True):
+        """dopt_run_sparse: T rounds of D-SGD on a sparse context (load_shards_csr); arguments and
+        return value as run_gt."""
+        T = int(T)
+        obj = np.zeros(T) if objective else None
+        cons = np.zeros(T) if consensus else None
+        tim = np.zeros(T) if want_time else None
+        if idx is not None:
+            idx = np.ascontiguousarray(idx, dtype=np.int32)
+        flags = (RUN_OBJECTIVE if objective else 0) | (RUN_CONSENSUS if consensus else 0)
+        check(lib().dopt_run_sparse(self._h, int(t0), T, float(eta0), int(batch), _ptr(idx), float(lam_grad),
+                                    float(lam_obj), float(f_opt), flags, _ptr(obj), _ptr(cons), _ptr(tim)))
         return obj, cons, tim
 
     def gt_set_state(self, y=None, g=None):

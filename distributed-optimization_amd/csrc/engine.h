@@ -292,6 +292,38 @@ hipError_t launch_softmax_f32(const SoftmaxArgs& a, int n_workers, hipStream_t s
 hipError_t launch_softmax_f64(const SoftmaxArgs& a, int n_workers, hipStream_t s);
 hipError_t launch_softmax_x32(const SoftmaxArgs& a, int n_workers, hipStream_t s);
 
+// ---- sparse shards (k_round_sparse.inc): the D-SGD round over shards stored in CSR, one launch per
+// round, one workgroup of 256 threads per worker
+//   g_i = (1/b) X_i^T r(X_i x_i) + lam x_i,   x_i' = sum_j W_ij x_j - eta g_i
+// r: the D-SGD round's arguments (X unused; y the labels in the storage type, off the shards' row
+// offsets, idx / b, x_old / x_new, xbar, the CSR mixing matrix, eta, lam, the slabs); r.ld the state
+// row stride and r.nchunks its 16-byte STATE chunks.  r.flags: F_STEP, F_CONS, F_LOSS (every row of
+// the shard: idx must be null).  No halo rows, no F_MEAN.
+struct SparseArgs {
+  RoundArgs r;
+  // row view: CSR over the global rows
+  const int64_t* row_ptr;  // [rows + 1]
+  const int32_t* col;      // [nnz] ascending within a row
+  const void* val;         // [nnz] S
+  // column view: worker i's entries sorted by (column, local row) at [row_ptr[off[i]], row_ptr[off[i + 1]]);
+  // its support columns scol[sup_off[i] .. sup_off[i + 1]) -- the short ones first -- with extents
+  // sptr[sup_off[i] + i ..] (one more entry than columns), relative to the worker's first entry
+  const int32_t* srow;     // [nnz] local row
+  const void* sval;        // [nnz] S
+  const int64_t* sup_off;  // [n + 1]
+  const int32_t* scol;
+  const int32_t* sptr;
+  const int32_t* n_short;  // [n] support columns walked by one thread each; the others take a wave
+  int32_t max_m;           // rows of the largest shard (the residual array in LDS)
+  int32_t all_wave;        // A/B: every support column by a wave
+};
+constexpr int64_t kSparseMaxD = 1 << 20;
+constexpr int64_t kSparseMaxRows = 16384;  // the residuals of a shard in LDS: 128 KiB of float64
+// per element-type pair (sparse_f32.hip / sparse_f64.hip / sparse_x32.hip)
+hipError_t launch_sparse_f32(int problem, const SparseArgs& a, int n_workers, hipStream_t s);
+hipError_t launch_sparse_f64(int problem, const SparseArgs& a, int n_workers, hipStream_t s);
+hipError_t launch_sparse_x32(int problem, const SparseArgs& a, int n_workers, hipStream_t s);
+
 // ---- large d (column-blocked): one workgroup per (worker, group of 64-chunk column blocks)
 constexpr int kSplitMaxRows = 64;  // rows held in registers by a step workgroup (16 per wave)
 // Step: g_i = (1/nb) sum_k coef_k x_k + lam x_i, x_i' = mix - eta g_i (block by block); with

@@ -14,6 +14,7 @@
 //   G      [N x ld]     T   per-worker gradients (centralized trainer, multi-GPU phases)
 //   ys[2], gprev [N x ld] T   gradient tracking: tracker ping-pong, previous stochastic gradients
 //   xh[2]  [N x ld]     T   CHOCO-SGD: ping-pong of the public copies xhat
+//   sp_*                    sparse contexts (dopt_load_shards_csr): no X; the shards' CSR row view and column view
 //
 // Launch schedule of one D-SGD round t (metrics every round):
 //   k_round(t)       grad + mix + step for every worker, and the consensus /
@@ -23,7 +24,7 @@
 // plus one metrics-only pass after the last round.  Only a separate objective dataset
 // (X_full that is not the shards) takes a metrics-only pass every round.
 // A gradient-tracking round (dopt_run_gt) has the same schedule with k_round_gt in k_round's place,
-// a CHOCO-SGD round (dopt_run_choco) with k_round_choco.
+// a CHOCO-SGD round (dopt_run_choco) with k_round_choco, a round over CSR shards (dopt_run_sparse) with k_round_sparse.
 // The multi-GPU phase functions (dopt_phase_*) split the same round at its
 // communication points; distributed.py drives them.
 #include <hip/hip_runtime.h>
@@ -154,6 +155,19 @@ struct dopt_ctx {
   // softmax regression (dopt_load_shards_softmax): classes of the context, 0 for the vector objectives.  The
   // state rows (xs, xbar, part, S) then hold sm_C blocks of ld elements, class-major; ld / nch stay the data row's
   int sm_C = 0;
+  // sparse shards (dopt_load_shards_csr): X stays empty; the shards are the CSR row view (sp_rp over the global
+  // rows, sp_col, sp_val) and the doubly compressed column view (k_round_sparse.inc, SparseArgs)
+  bool sparse = false;
+  int64_t* sp_rp = nullptr;
+  int32_t* sp_col = nullptr;
+  void* sp_val = nullptr;
+  int32_t* sp_srow = nullptr;
+  void* sp_sval = nullptr;
+  int64_t* sp_supoff = nullptr;
+  int32_t* sp_scol = nullptr;
+  int32_t* sp_sptr = nullptr;
+  int32_t* sp_nshort = nullptr;
+  std::vector<int64_t> sp_rp_h;  // host copy of sp_rp (dopt_get_shard)
   void* xbar[2] = {nullptr, nullptr};
   int xb = 0;  // xbar[xb] = average of the current iterates
   double* S = nullptr;             // [ld] column sums of the current iterates (complete-graph mixing)
@@ -515,12 +529,28 @@ int alloc_state(dopt_ctx* c) {
   return DOPT_OK;
 }
 
+void free_sparse(dopt_ctx* c) {
+  c->sparse = false;
+  dfree_t(c->sp_rp);
+  dfree_t(c->sp_col);
+  dfree(c->sp_val);
+  dfree_t(c->sp_srow);
+  dfree(c->sp_sval);
+  dfree_t(c->sp_supoff);
+  dfree_t(c->sp_scol);
+  dfree_t(c->sp_sptr);
+  dfree_t(c->sp_nshort);
+  c->sp_rp_h.clear();
+  c->sp_rp_h.shrink_to_fit();
+}
+
 // n_classes > 0: a softmax context (dopt_load_shards_softmax), else one of the vector objectives.
 int set_layout(dopt_ctx* c, int problem, int64_t n, int64_t d, int64_t n_classes = 0) {
   c->carry_pending = false;
   c->rs_live = c->rs_gram_ok = false;  // new data: the row-space state and the Gram matrices are gone
   c->rs_wg = 0;
   c->sm_C = 0;
+  free_sparse(c);  // loading or generating other shards makes the context ordinary again
   if (problem == DOPT_SOFTMAX && n_classes == 0)
     return fail(DOPT_ERR_UNSUPPORTED, "softmax shards are loaded by dopt_load_shards_softmax (there is no softmax "
                 "generator)");
@@ -1287,6 +1317,13 @@ int no_softmax(const char* fn) {
               "are dopt_run_softmax, its iterates dopt_softmax_set_models / dopt_softmax_get_models", fn);
 }
 
+// ... and a sparse context (dopt_load_shards_csr), whose shards the dense kernels cannot read.
+int no_dense(const dopt_ctx* c, const char* fn) {
+  if (c->sm_C) return no_softmax(fn);
+  return fail(DOPT_ERR_UNSUPPORTED, "%s: not available on a sparse context (dopt_load_shards_csr); its rounds are "
+              "dopt_run_sparse", fn);
+}
+
 int check_run(dopt_ctx* c, int64_t T, int64_t batch, const int32_t* idx, bool need_topo) {
   if (!c->have_data) return fail(DOPT_ERR_STATE, "no shards loaded");
   if (need_topo && !c->have_topo) return fail(DOPT_ERR_STATE, "no topology set");
@@ -1401,6 +1438,7 @@ int dopt_destroy(dopt_ctx* c) {
   dfree_t(c->cpart);
   dfree_t(c->send_ids);
   dfree_t(c->stamps);
+  free_sparse(c);
   for (double** p : {&c->rs_coef, &c->rs_up, &c->rs_cp, &c->rs_z, &c->rs_gram, &c->rs_dpart, &c->rs_Z, &c->rs_x0d})
     dfree_t(*p);
   dfree(c->rs_x0buf);
@@ -1505,7 +1543,7 @@ int dopt_generate_shards(dopt_ctx* c, int problem, int64_t n_workers, int64_t d,
 }
 
 int dopt_load_objective_data(dopt_ctx* c, int64_t n_rows, const void* X, const void* y, int src_f32) {
-  if (c && c->sm_C) return no_softmax(__func__);
+  if (c && (c->sm_C || c->sparse)) return no_dense(c, __func__);
   CHECK_ARG(c, "ctx is NULL");
   if (!c->have_data) return fail(DOPT_ERR_STATE, "load the shards first");
   CHECK_ARG(n_rows >= 0, "n_rows must be >= 0");
@@ -1544,6 +1582,24 @@ int dopt_get_shard(dopt_ctx* c, int64_t worker, double* X_out, double* y_out) {
   int rc;
   if ((rc = set_device(c))) return rc;
   const int64_t r0 = c->off_h[(size_t)worker], nr = c->off_h[(size_t)worker + 1] - r0;
+  if (c->sparse) {  // the densified shard
+    const int64_t e0 = c->sp_rp_h[(size_t)r0], ne = c->sp_rp_h[(size_t)(r0 + nr)] - e0;
+    std::vector<int32_t> cj((size_t)ne);
+    std::vector<char> v((size_t)ne * c->xesz);
+    if (X_out && ne > 0) {
+      HIPOK(hipMemcpy(cj.data(), c->sp_col + e0, cj.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+      HIPOK(hipMemcpy(v.data(), (const char*)c->sp_val + e0 * (int64_t)c->xesz, v.size(), hipMemcpyDeviceToHost));
+    }
+    if (X_out) {
+      std::fill(X_out, X_out + nr * c->d, 0.0);
+      for (int64_t r = 0; r < nr; ++r)
+        for (int64_t e = c->sp_rp_h[(size_t)(r0 + r)] - e0; e < c->sp_rp_h[(size_t)(r0 + r + 1)] - e0; ++e)
+          X_out[r * c->d + cj[(size_t)e]] = c->xdtype == DOPT_F32 ? (double)((const float*)v.data())[e]
+                                                                   : ((const double*)v.data())[e];
+    }
+    if (y_out && (rc = download_rows(c, c->xdtype, (const char*)c->y + r0 * (int64_t)c->xesz, y_out, nr, 1, 1))) return rc;
+    return DOPT_OK;
+  }
   if (X_out && c->tiled && nr > 0) {  // the worker's rows out of the tiles, row-major, then down
     void* tmp = nullptr;
     if ((rc = dalloc_t(&tmp, (size_t)(nr * c->ldx) * c->xesz))) return rc;
@@ -1612,7 +1668,7 @@ int dopt_set_topology(dopt_ctx* c, int64_t n_workers, const int64_t* row_ptr, co
 }
 
 int dopt_set_mixing_mean(dopt_ctx* c, int64_t n_workers, double w_off, const double* w_diag) {
-  if (c && c->sm_C) return no_softmax(__func__);
+  if (c && (c->sm_C || c->sparse)) return no_dense(c, __func__);
   CHECK_ARG(c && w_diag, "NULL argument");
   if (!c->have_data) return fail(DOPT_ERR_STATE, "load the shards first");
   CHECK_ARG(n_workers == c->n, "mixing has %lld workers, data has %lld", (long long)n_workers, (long long)c->n);
@@ -1672,7 +1728,7 @@ int dopt_get_models(dopt_ctx* c, double* x) {
 }
 
 int dopt_set_global(dopt_ctx* c, const double* x) {
-  if (c && c->sm_C) return no_softmax(__func__);
+  if (c && (c->sm_C || c->sparse)) return no_dense(c, __func__);
   CHECK_ARG(c && x, "NULL argument");
   if (!c->have_data) return fail(DOPT_ERR_STATE, "load the shards first");
   int rc;
@@ -1681,7 +1737,7 @@ int dopt_set_global(dopt_ctx* c, const double* x) {
 }
 
 int dopt_get_global(dopt_ctx* c, double* x) {
-  if (c && c->sm_C) return no_softmax(__func__);
+  if (c && (c->sm_C || c->sparse)) return no_dense(c, __func__);
   CHECK_ARG(c && x, "NULL argument");
   if (!c->have_data) return fail(DOPT_ERR_STATE, "load the shards first");
   int rc;
@@ -1826,7 +1882,7 @@ static int run_dsgd(dopt_ctx* c, int64_t t0, int64_t T, double eta0, int64_t bat
 int dopt_run_dsgd(dopt_ctx* c, int64_t t0, int64_t T, double eta0, int64_t batch, const int32_t* idx,
                   double lam_grad, double lam_obj, double f_opt, uint32_t flags, double* obj_out,
                   double* cons_out, double* time_out) {
-  if (c && c->sm_C) return no_softmax(__func__);
+  if (c && (c->sm_C || c->sparse)) return no_dense(c, __func__);
   return run_dsgd(c, t0, T, eta0, batch, idx, lam_grad, lam_obj, f_opt, flags, obj_out, cons_out, time_out, false,
                   nullptr);
 }
@@ -1834,7 +1890,7 @@ int dopt_run_dsgd(dopt_ctx* c, int64_t t0, int64_t T, double eta0, int64_t batch
 int dopt_run_dsgd_pipelined(dopt_ctx* c, int64_t t0, int64_t T, double eta0, int64_t batch, const int32_t* idx,
                             double lam_grad, double lam_obj, double f_opt, uint32_t flags, double* obj_out,
                             double* cons_out, double* time_out, int64_t* n_out) {
-  if (c && c->sm_C) return no_softmax(__func__);
+  if (c && (c->sm_C || c->sparse)) return no_dense(c, __func__);
   CHECK_ARG(n_out, "n_out is NULL");
   return run_dsgd(c, t0, T, eta0, batch, idx, lam_grad, lam_obj, f_opt, flags, obj_out, cons_out, time_out, true,
                   n_out);
@@ -1843,7 +1899,7 @@ int dopt_run_dsgd_pipelined(dopt_ctx* c, int64_t t0, int64_t T, double eta0, int
 int dopt_run_centralized(dopt_ctx* c, int64_t t0, int64_t T, double eta0, int64_t batch,
                          const int32_t* idx, double lam_grad, double lam_obj, double f_opt,
                          uint32_t flags, double* obj_out, double* time_out) {
-  if (c && c->sm_C) return no_softmax(__func__);
+  if (c && (c->sm_C || c->sparse)) return no_dense(c, __func__);
   CHECK_ARG(c, "ctx is NULL");
   c->carry_pending = false;
   int rc;
@@ -2029,12 +2085,12 @@ int run_gt(dopt_ctx* c, int64_t t0, int64_t T, double eta0, int64_t batch, const
 int dopt_run_gt(dopt_ctx* c, int64_t t0, int64_t T, double eta0, int64_t batch, const int32_t* idx, double lam_grad,
                 double lam_obj, double f_opt, uint32_t flags, double* obj_out, double* cons_out,
                 double* time_out) {
-  if (c && c->sm_C) return no_softmax(__func__);
+  if (c && (c->sm_C || c->sparse)) return no_dense(c, __func__);
   return run_gt(c, t0, T, eta0, batch, idx, lam_grad, lam_obj, f_opt, flags, obj_out, cons_out, time_out);
 }
 
 int dopt_gt_set_state(dopt_ctx* c, const double* y, const double* g) {
-  if (c && c->sm_C) return no_softmax(__func__);
+  if (c && (c->sm_C || c->sparse)) return no_dense(c, __func__);
   CHECK_ARG(c, "ctx is NULL");
   int rc;
   if ((rc = check_gt(c))) return rc;
@@ -2056,7 +2112,7 @@ int dopt_gt_set_state(dopt_ctx* c, const double* y, const double* g) {
 }
 
 int dopt_gt_get_state(dopt_ctx* c, double* y, double* g) {
-  if (c && c->sm_C) return no_softmax(__func__);
+  if (c && (c->sm_C || c->sparse)) return no_dense(c, __func__);
   CHECK_ARG(c, "ctx is NULL");
   int rc;
   if ((rc = check_gt(c))) return rc;
@@ -2203,13 +2259,13 @@ int run_choco(dopt_ctx* c, int64_t t0, int64_t T, double eta0, int64_t batch, co
 int dopt_run_choco(dopt_ctx* c, int64_t t0, int64_t T, double eta0, int64_t batch, const int32_t* idx,
                    double lam_grad, double lam_obj, double f_opt, uint32_t flags, int64_t k, double gamma,
                    double* obj_out, double* cons_out, double* time_out) {
-  if (c && c->sm_C) return no_softmax(__func__);
+  if (c && (c->sm_C || c->sparse)) return no_dense(c, __func__);
   return run_choco(c, t0, T, eta0, batch, idx, lam_grad, lam_obj, f_opt, flags, k, gamma, obj_out, cons_out,
                    time_out);
 }
 
 int dopt_choco_set_state(dopt_ctx* c, const double* xhat) {
-  if (c && c->sm_C) return no_softmax(__func__);
+  if (c && (c->sm_C || c->sparse)) return no_dense(c, __func__);
   CHECK_ARG(c, "ctx is NULL");
   int rc;
   if ((rc = check_choco(c))) return rc;
@@ -2225,7 +2281,7 @@ int dopt_choco_set_state(dopt_ctx* c, const double* xhat) {
 }
 
 int dopt_choco_get_state(dopt_ctx* c, double* xhat) {
-  if (c && c->sm_C) return no_softmax(__func__);
+  if (c && (c->sm_C || c->sparse)) return no_dense(c, __func__);
   CHECK_ARG(c, "ctx is NULL");
   CHECK_ARG(xhat, "xhat is NULL");
   int rc;
@@ -2362,6 +2418,247 @@ int dopt_softmax_get_models(dopt_ctx* c, double* x) {
   return download_rows(c, c->dtype, c->xs[c->cur], x, c->n * c->sm_C, c->d, c->ld);
 }
 
+// ---------------------------------------------------------------------------- sparse (CSR) shards
+namespace {
+
+constexpr int kSparseLongMin = 32;  // support columns with at least this many entries take a wave
+
+hipError_t launch_sparse(dopt_ctx* c, const SparseArgs& g) {
+  if (c->dtype == DOPT_F32) return launch_sparse_f32(c->problem, g, (int)c->n, c->stream);
+  if (c->xdtype == DOPT_F32) return launch_sparse_x32(c->problem, g, (int)c->n, c->stream);
+  return launch_sparse_f64(c->problem, g, (int)c->n, c->stream);
+}
+
+// Host values (float32 or float64) in the storage type of the context.
+std::vector<char> to_storage(const dopt_ctx* c, const void* src, int src_f32, int64_t n) {
+  std::vector<char> out((size_t)n * c->xesz);
+  for (int64_t k = 0; k < n; ++k) {
+    const double v = src_f32 ? (double)((const float*)src)[k] : ((const double*)src)[k];
+    if (c->xdtype == DOPT_F32) ((float*)out.data())[k] = (float)v;
+    else ((double*)out.data())[k] = v;
+  }
+  return out;
+}
+
+// T rounds of D-SGD over CSR shards on run_gt's schedule: k_round_sparse, then the column sums of the
+// new iterates with the history row of the previous round folded in.  Round h's launch takes the
+// metrics of x_h at xbar_h (history[h - 1]) in its pass -- the objective only when the batch is the
+// whole shard; with minibatch indices the objective is one more launch of the same kernel without
+// the step, over every row -- and the row of the last iterates is the same launch without the step,
+// folded by the same column-sum launch: a run split into several calls gives the bits of one call.
+int run_sparse(dopt_ctx* c, int64_t t0, int64_t T, double eta0, int64_t batch, const int32_t* idx, double lam_grad,
+               double lam_obj, double f_opt, uint32_t flags, double* obj_out, double* cons_out, double* time_out) {
+  CHECK_ARG(c, "ctx is NULL");
+  int rc;
+  if (!c->have_data) return fail(DOPT_ERR_STATE, "no shards loaded");
+  if (!c->sparse) return fail(DOPT_ERR_STATE, "not a sparse context: load the shards with dopt_load_shards_csr");
+  if (!c->have_topo) return fail(DOPT_ERR_STATE, "no topology set");
+  if (c->mean_mix || c->n_halo > 0 || c->n_send > 0 || c->sptr || c->obj_sep)  // (their setters refuse the context)
+    return fail(DOPT_ERR_UNSUPPORTED, "sparse shards: CSR mixing on one device over the shards' own rows only");
+  if (!idx && batch < c->max_m && c->sampler == DOPT_SAMPLE_DEVICE)
+    return fail(DOPT_ERR_UNSUPPORTED, "sparse shards: the device sampler is not supported; pass idx");
+  if ((rc = check_run(c, T, batch, idx, true))) return rc;
+  if ((rc = set_device(c))) return rc;
+  if (T == 0) return DOPT_OK;
+  if ((rc = ensure_hist(c, T + 1))) return rc;
+  const bool want_obj = flags & DOPT_RUN_OBJECTIVE, want_cons = flags & DOPT_RUN_CONSENSUS;
+  const bool metrics = want_obj || want_cons;
+  const bool fuse_loss = want_obj && !idx;  // the step's row pass walks every row of the shard
+  const char* aw_env = getenv("DOPT_SPARSE_ALLWAVE");  // A/B knob, read per call: 1 = every support column by a wave
+  const bool all_wave = aw_env && atoi(aw_env) != 0;
+  const int64_t CH = idx ? idx_chunk_rounds(c, T, batch) : 1;
+  int& xb = c->xb;
+  if ((rc = colsum_current(c))) return rc;  // xbar of the starting iterates
+  HIPOK(launch_stamp(c->stamps, c->stream));
+
+  auto sp_args = [&](int32_t kflags) {
+    SparseArgs g;
+    memset(&g, 0, sizeof(g));
+    g.r = base_args(c);
+    g.r.nchunks = (int32_t)c->nchs;  // 16-byte chunks of the state row
+    g.r.x_old = c->xs[c->cur];
+    g.r.x_new = c->xs[c->cur ^ 1];
+    g.r.xbar = c->xbar[xb];
+    g.r.lam = lam_grad;
+    g.r.b = batch;
+    g.r.flags = kflags;
+    g.row_ptr = c->sp_rp;
+    g.col = c->sp_col;
+    g.val = c->sp_val;
+    g.srow = c->sp_srow;
+    g.sval = c->sp_sval;
+    g.sup_off = c->sp_supoff;
+    g.scol = c->sp_scol;
+    g.sptr = c->sp_sptr;
+    g.n_short = c->sp_nshort;
+    g.max_m = (int32_t)c->max_m;
+    g.all_wave = all_wave ? 1 : 0;
+    if (kflags & F_LOSS) c->loss_groups = c->n;  // per-worker loss slabs
+    return g;
+  };
+  // history row `row` = the slabs of the launches at xbar[xb]
+  auto fold_args = [&](int64_t row) {
+    double* hr = c->hraw + 3 * row;
+    return FoldArgs{want_cons ? c->slab_cons : nullptr, c->n, want_obj ? c->slab_loss : nullptr, c->loss_groups,
+                    want_obj ? c->xbar[xb] : nullptr, hr, hr + 1, hr + 2};
+  };
+
+  for (int64_t h = 0; h < T; ++h) {
+    const int64_t t = t0 + h;
+    if (idx && h % CH == 0) {
+      if ((rc = upload_idx_chunk(c, idx, h, std::min(CH, T - h), batch))) return rc;
+    }
+    const bool met = metrics && h > 0;
+    if (c->prof && (rc = prof_event(c, false))) return rc;
+    if (met && want_obj && !fuse_loss) HIPOK(launch_sparse(c, sp_args(F_LOSS)));  // the objective of x_h's row
+    SparseArgs g = sp_args(F_STEP | (met && want_cons ? F_CONS : 0) | (met && fuse_loss ? F_LOSS : 0));
+    g.r.idx = idx ? c->idx + (h % CH) * c->n * batch : nullptr;
+    g.r.eta = eta0 / sqrt((double)(t + 1));  // trainer.py:138-140
+    HIPOK(launch_sparse(c, g));
+    if (c->prof && (rc = prof_event(c, true))) return rc;
+    // xbar_{t+1} (trainer.py:182) and the stamp of the end of round t's update; history[h - 1] rides the launch
+    const FoldArgs fold = fold_args(met ? h - 1 : 0);
+    HIPOK(launch_colsum(c->dtype, c->xs[c->cur ^ 1], c->n, c->ld, (int32_t)c->nchs, kRowsPerGroup, c->part,
+                        c->stamps + h + 1, c->n, c->xbar[xb ^ 1], nullptr, 0.0, 0, c->stream, c->S,
+                        met ? &fold : nullptr));
+    c->cur ^= 1;
+    xb ^= 1;
+  }
+  if (metrics) {  // the row of the last iterates; the column sums land in the spare xbar
+    HIPOK(launch_sparse(c, sp_args((want_obj ? F_LOSS : 0) | (want_cons ? F_CONS : 0))));
+    const FoldArgs fold = fold_args(T - 1);
+    HIPOK(launch_colsum(c->dtype, c->xs[c->cur], c->n, c->ld, (int32_t)c->nchs, kRowsPerGroup, c->part, nullptr, c->n,
+                        c->xbar[xb ^ 1], nullptr, 0.0, 0, c->stream, c->S, &fold));
+  }
+  return finish_run(c, T, T, lam_obj, f_opt, want_obj ? obj_out : nullptr, want_cons ? cons_out : nullptr,
+                    time_out);
+}
+
+}  // namespace
+
+int dopt_load_shards_csr(dopt_ctx* c, int problem, int64_t n_workers, int64_t d, const int64_t* off,
+                         const int64_t* row_ptr, const int32_t* col, const void* val, const void* y, int src_f32) {
+  CHECK_ARG(c, "ctx is NULL");
+  CHECK_ARG(off && row_ptr, "shard_offsets / row_ptr are NULL");
+  if (problem != DOPT_LOGISTIC && problem != DOPT_QUADRATIC)
+    return fail(DOPT_ERR_UNSUPPORTED, "sparse shards: problem %d (logistic or quadratic)", problem);
+  if (d > kSparseMaxD)
+    return fail(DOPT_ERR_UNSUPPORTED, "sparse shards: d = %lld above %lld", (long long)d, (long long)kSparseMaxD);
+  int rc;
+  if ((rc = set_device(c))) return rc;
+  c->have_data = false;
+  if ((rc = set_layout(c, problem, n_workers, d))) return rc;
+  c->split = c->tiled = false;  // the state rows are walked in 16-byte chunks whatever their length
+  c->ldx = c->ld;
+  CHECK_ARG(off[0] == 0, "shard_offsets[0] must be 0");
+  int64_t max_m = 0, min_m = off[1] - off[0];
+  for (int64_t i = 0; i < n_workers; ++i) {
+    CHECK_ARG(off[i + 1] >= off[i], "shard_offsets must be non-decreasing");
+    max_m = std::max(max_m, off[i + 1] - off[i]);
+    min_m = std::min(min_m, off[i + 1] - off[i]);
+  }
+  if (max_m > kSparseMaxRows)
+    return fail(DOPT_ERR_UNSUPPORTED, "sparse shards: a shard of %lld rows; the residuals of a shard stay in LDS (at "
+                "most %lld rows)", (long long)max_m, (long long)kSparseMaxRows);
+  const int64_t rows = off[n_workers];
+  CHECK_ARG(row_ptr[0] == 0, "row_ptr[0] must be 0");
+  for (int64_t r = 0; r < rows; ++r) CHECK_ARG(row_ptr[r + 1] >= row_ptr[r], "row_ptr not monotone at row %lld", (long long)r);
+  const int64_t nnz = row_ptr[rows];
+  CHECK_ARG(nnz == 0 || (col && val), "col / val are NULL");
+  CHECK_ARG(rows == 0 || y, "y is NULL");
+  for (int64_t i = 0; i < n_workers; ++i)
+    if (row_ptr[off[i + 1]] - row_ptr[off[i]] >= (1LL << 31))
+      return fail(DOPT_ERR_UNSUPPORTED, "sparse shards: shard %lld holds 2^31 non-zeros or more", (long long)i);
+  for (int64_t r = 0; r < rows; ++r)
+    for (int64_t e = row_ptr[r]; e < row_ptr[r + 1]; ++e) {
+      CHECK_ARG(col[e] >= 0 && col[e] < d, "row %lld: column %d outside [0, %lld)", (long long)r, col[e], (long long)d);
+      CHECK_ARG(e == row_ptr[r] || col[e] > col[e - 1], "row %lld: columns must be strictly ascending (%d after %d)",
+                (long long)r, col[e], col[e - 1]);
+    }
+  int long_min = kSparseLongMin;
+  if (const char* v = getenv("DOPT_SPARSE_LONG"))  // tuning knob, read at load: the short / long split
+    if (atoi(v) >= 1) long_min = atoi(v);
+
+  // the column view: per worker, the entries sorted by (column, local row) -- key = column, then the
+  // entry's position in the shard, which ascends with the row -- as runs of one column each, the short
+  // runs first
+  const std::vector<char> hval = to_storage(c, val, src_f32, nnz), hy = to_storage(c, y, src_f32, rows);
+  std::vector<char> sval((size_t)nnz * c->xesz);
+  std::vector<int32_t> srow((size_t)nnz), scol, sptr, nshort((size_t)n_workers);
+  std::vector<int64_t> supoff((size_t)n_workers + 1, 0);
+  std::vector<uint64_t> key;
+  std::vector<int32_t> lrow;
+  struct Run { int32_t col, pos, len; };
+  std::vector<Run> runs;
+  for (int64_t i = 0; i < n_workers; ++i) {
+    const int64_t base = row_ptr[off[i]], cnt = row_ptr[off[i + 1]] - base;
+    key.resize((size_t)cnt);
+    lrow.resize((size_t)cnt);
+    for (int64_t r = off[i]; r < off[i + 1]; ++r)
+      for (int64_t e = row_ptr[r]; e < row_ptr[r + 1]; ++e) {
+        key[(size_t)(e - base)] = ((uint64_t)(uint32_t)col[e] << 32) | (uint64_t)(e - base);
+        lrow[(size_t)(e - base)] = (int32_t)(r - off[i]);
+      }
+    std::sort(key.begin(), key.end());
+    runs.clear();
+    for (int64_t k = 0; k < cnt; ++k) {
+      const int32_t cj = (int32_t)(key[(size_t)k] >> 32);
+      if (runs.empty() || runs.back().col != cj) runs.push_back(Run{cj, (int32_t)k, 0});
+      ++runs.back().len;
+    }
+    int32_t out = 0, ns_short = 0;
+    for (int pass = 0; pass < 2; ++pass)  // short columns, then long ones, each list by ascending column
+      for (const Run& q : runs) {
+        if ((q.len >= long_min) != (pass == 1)) continue;
+        scol.push_back(q.col);
+        sptr.push_back(out);
+        ns_short += pass == 0;
+        for (int32_t k = q.pos; k < q.pos + q.len; ++k, ++out) {
+          const int64_t e = (int64_t)(key[(size_t)k] & 0xffffffffu);
+          srow[(size_t)(base + out)] = lrow[(size_t)e];
+          memcpy(&sval[(size_t)(base + out) * c->xesz], &hval[(size_t)(base + e) * c->xesz], c->xesz);
+        }
+      }
+    sptr.push_back(out);  // one more extent than columns, per worker
+    nshort[(size_t)i] = ns_short;
+    supoff[(size_t)i + 1] = (int64_t)scol.size();
+  }
+
+  auto upload_vec = [](auto** dst, const void* src, size_t bytes) -> int {
+    int rc = dalloc_t(dst, bytes);
+    if (rc) return rc;
+    if (bytes) HIPOK(hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice));
+    return DOPT_OK;
+  };
+  c->rows = rows;
+  c->max_m = max_m;
+  c->min_m = min_m;
+  c->off_h.assign(off, off + n_workers + 1);
+  c->sp_rp_h.assign(row_ptr, row_ptr + rows + 1);
+  dfree(c->X);  // no dense rows
+  if ((rc = upload_vec(&c->off, off, (size_t)(n_workers + 1) * sizeof(int64_t)))) return rc;
+  if ((rc = upload_vec(&c->y, hy.data(), hy.size()))) return rc;
+  if ((rc = upload_vec(&c->sp_rp, row_ptr, (size_t)(rows + 1) * sizeof(int64_t)))) return rc;
+  if ((rc = upload_vec(&c->sp_col, col, (size_t)nnz * sizeof(int32_t)))) return rc;
+  if ((rc = upload_vec(&c->sp_val, hval.data(), hval.size()))) return rc;
+  if ((rc = upload_vec(&c->sp_srow, srow.data(), srow.size() * sizeof(int32_t)))) return rc;
+  if ((rc = upload_vec(&c->sp_sval, sval.data(), sval.size()))) return rc;
+  if ((rc = upload_vec(&c->sp_supoff, supoff.data(), supoff.size() * sizeof(int64_t)))) return rc;
+  if ((rc = upload_vec(&c->sp_scol, scol.data(), scol.size() * sizeof(int32_t)))) return rc;
+  if ((rc = upload_vec(&c->sp_sptr, sptr.data(), sptr.size() * sizeof(int32_t)))) return rc;
+  if ((rc = upload_vec(&c->sp_nshort, nshort.data(), nshort.size() * sizeof(int32_t)))) return rc;
+  if ((rc = alloc_state(c))) return rc;  // the iterates start at zero
+  c->sparse = true;
+  c->have_data = true;
+  return DOPT_OK;
+}
+
+int dopt_run_sparse(dopt_ctx* c, int64_t t0, int64_t T, double eta0, int64_t batch, const int32_t* idx,
+                    double lam_grad, double lam_obj, double f_opt, uint32_t flags, double* obj_out, double* cons_out,
+                    double* time_out) {
+  return run_sparse(c, t0, T, eta0, batch, idx, lam_grad, lam_obj, f_opt, flags, obj_out, cons_out, time_out);
+}
+
 // ---------------------------------------------------------------------------- single evaluations
 namespace {
 // Rows longer than the row-resident kernel holds (d > 2048 in float64): dots over column
@@ -2489,7 +2786,7 @@ int dopt_eval_objective(dopt_ctx* c, int problem, int64_t n, int64_t d, const do
 }
 
 int dopt_eval_full(dopt_ctx* c, const double* w, double reg, double* f_out, double* g_out) {
-  if (c && c->sm_C) return no_softmax(__func__);
+  if (c && (c->sm_C || c->sparse)) return no_dense(c, __func__);
   CHECK_ARG(c && w && f_out, "NULL argument");
   if (!c->have_data) return fail(DOPT_ERR_STATE, "no shards loaded");
   int rc;
@@ -2557,7 +2854,7 @@ int dopt_set_sampler(dopt_ctx* c, int mode, uint64_t seed, int64_t first_worker)
 }
 
 int dopt_phase_set_round(dopt_ctx* c, int64_t t) {
-  if (c && c->sm_C) return no_softmax(__func__);
+  if (c && (c->sm_C || c->sparse)) return no_dense(c, __func__);
   CHECK_ARG(c, "ctx is NULL");
   CHECK_ARG(t >= 0, "round must be >= 0");
   c->ph_round = t;
@@ -2565,7 +2862,7 @@ int dopt_phase_set_round(dopt_ctx* c, int64_t t) {
 }
 
 int dopt_phase_set_step(dopt_ctx* c, int64_t t, double eta0) {
-  if (c && c->sm_C) return no_softmax(__func__);
+  if (c && (c->sm_C || c->sparse)) return no_dense(c, __func__);
   CHECK_ARG(c, "ctx is NULL");
   CHECK_ARG(t >= 0, "round must be >= 0");
   c->ph_round = t;
@@ -2616,7 +2913,7 @@ int dopt_get_layout(dopt_ctx* c, int64_t* ld, int64_t* elem_bytes) {
 }
 
 int dopt_set_partition(dopt_ctx* c, int64_t n_global, int64_t rows_global) {
-  if (c && c->sm_C) return no_softmax(__func__);
+  if (c && (c->sm_C || c->sparse)) return no_dense(c, __func__);
   CHECK_ARG(c, "ctx is NULL");
   if (!c->have_data) return fail(DOPT_ERR_STATE, "load the shards first");
   CHECK_ARG(n_global >= c->n && rows_global >= 0, "global sizes smaller than the local slice");
@@ -2629,7 +2926,7 @@ int dopt_set_partition(dopt_ctx* c, int64_t n_global, int64_t rows_global) {
 
 int dopt_set_halo(dopt_ctx* c, int64_t n_halo, void* halo_dev, int64_t n_send, void* send_dev,
                   const int32_t* send_ids) {
-  if (c && c->sm_C) return no_softmax(__func__);
+  if (c && (c->sm_C || c->sparse)) return no_dense(c, __func__);
   CHECK_ARG(c, "ctx is NULL");
   if (!c->have_data) return fail(DOPT_ERR_STATE, "load the shards first");
   CHECK_ARG(n_halo >= 0 && n_send >= 0, "negative sizes");
@@ -2669,7 +2966,7 @@ int dopt_set_halo(dopt_ctx* c, int64_t n_halo, void* halo_dev, int64_t n_send, v
 }
 
 int dopt_phase_gather(dopt_ctx* c) {
-  if (c && c->sm_C) return no_softmax(__func__);
+  if (c && (c->sm_C || c->sparse)) return no_dense(c, __func__);
   CHECK_ARG(c, "ctx is NULL");
   if (!c->have_data) return fail(DOPT_ERR_STATE, "no shards loaded");
   if (c->send_fresh) return DOPT_OK;  // the last mix wrote these rows already
@@ -2681,14 +2978,14 @@ int dopt_phase_gather(dopt_ctx* c) {
 }
 
 int dopt_phase_interior_count(dopt_ctx* c, int64_t* n_interior) {
-  if (c && c->sm_C) return no_softmax(__func__);
+  if (c && (c->sm_C || c->sparse)) return no_dense(c, __func__);
   CHECK_ARG(c && n_interior, "NULL argument");
   *n_interior = c->have_topo && !c->mean_mix && c->interior ? c->n_interior : 0;
   return DOPT_OK;
 }
 
 int dopt_phase_chain(dopt_ctx* c, int mark, int* was_pending) {
-  if (c && c->sm_C) return no_softmax(__func__);
+  if (c && (c->sm_C || c->sparse)) return no_dense(c, __func__);
   CHECK_ARG(c && was_pending, "NULL argument");
   *was_pending = c->carry_pending ? 1 : 0;
   c->carry_pending = mark != 0;
@@ -2697,7 +2994,7 @@ int dopt_phase_chain(dopt_ctx* c, int mark, int* was_pending) {
 }
 
 int dopt_phase_begin(dopt_ctx* c, int64_t batch) {
-  if (c && c->sm_C) return no_softmax(__func__);
+  if (c && (c->sm_C || c->sparse)) return no_dense(c, __func__);
   CHECK_ARG(c, "ctx is NULL");
   c->carry_pending = false;
   if (!c->have_data) return fail(DOPT_ERR_STATE, "no shards loaded");
@@ -2719,7 +3016,7 @@ int dopt_phase_begin(dopt_ctx* c, int64_t batch) {
 }
 
 int dopt_phase_grad(dopt_ctx* c, int64_t batch, const int32_t* idx, double lam_grad, uint32_t metric_flags) {
-  if (c && c->sm_C) return no_softmax(__func__);
+  if (c && (c->sm_C || c->sparse)) return no_dense(c, __func__);
   CHECK_ARG(c, "ctx is NULL");
   int rc;
   if ((rc = check_run(c, 1, batch, idx, false))) return rc;
@@ -2779,7 +3076,7 @@ int dopt_phase_grad(dopt_ctx* c, int64_t batch, const int32_t* idx, double lam_g
 }
 
 int dopt_phase_mix(dopt_ctx* c, int64_t t, double eta0) {
-  if (c && c->sm_C) return no_softmax(__func__);
+  if (c && (c->sm_C || c->sparse)) return no_dense(c, __func__);
   CHECK_ARG(c, "ctx is NULL");
   if (!c->have_topo || !c->G) return fail(DOPT_ERR_STATE, "topology / gradient phase missing");
   RoundArgs a = base_args(c);
@@ -2826,7 +3123,7 @@ int dopt_phase_mix(dopt_ctx* c, int64_t t, double eta0) {
 // ---- centralized trainer across ranks (trainer.py:41-71): per-rank gradients at the
 // shared iterate, all-reduced column sums of the gradients, the step.
 int dopt_phase_grad_shared(dopt_ctx* c, int64_t batch, const int32_t* idx, double lam_grad, int fuse_loss) {
-  if (c && c->sm_C) return no_softmax(__func__);
+  if (c && (c->sm_C || c->sparse)) return no_dense(c, __func__);
   CHECK_ARG(c, "ctx is NULL");
   int rc;
   if ((rc = check_run(c, 1, batch, idx, false))) return rc;
@@ -2859,7 +3156,7 @@ int dopt_phase_grad_shared(dopt_ctx* c, int64_t batch, const int32_t* idx, doubl
 }
 
 int dopt_phase_colsum_grad(dopt_ctx* c, double* sum_dev) {
-  if (c && c->sm_C) return no_softmax(__func__);
+  if (c && (c->sm_C || c->sparse)) return no_dense(c, __func__);
   CHECK_ARG(c && sum_dev, "NULL argument");
   if (!c->G) return fail(DOPT_ERR_STATE, "no gradient phase yet");
   HIPOK(launch_colsum_partial(c->dtype, c->G, c->n, c->ld, (int32_t)c->nchs, kRowsPerGroup, c->part, nullptr,
@@ -2870,7 +3167,7 @@ int dopt_phase_colsum_grad(dopt_ctx* c, double* sum_dev) {
 }
 
 int dopt_phase_central_step(dopt_ctx* c, const double* sum_dev, int64_t t, double eta0) {
-  if (c && c->sm_C) return no_softmax(__func__);
+  if (c && (c->sm_C || c->sparse)) return no_dense(c, __func__);
   CHECK_ARG(c && sum_dev, "NULL argument");
   HIPOK(launch_colsum_final(c->dtype, sum_dev, 1, n_div(c), c->ld, (int32_t)c->nchs, c->xg[c->gcur ^ 1],
                             c->xg[c->gcur], eta0 / sqrt((double)(t + 1)), 1, c->stream));
@@ -2879,7 +3176,7 @@ int dopt_phase_central_step(dopt_ctx* c, const double* sum_dev, int64_t t, doubl
 }
 
 int dopt_phase_metrics_pass_shared(dopt_ctx* c) {
-  if (c && c->sm_C) return no_softmax(__func__);
+  if (c && (c->sm_C || c->sparse)) return no_dense(c, __func__);
   CHECK_ARG(c, "ctx is NULL");
   if (c->split) {
     int rc;
@@ -2890,7 +3187,7 @@ int dopt_phase_metrics_pass_shared(dopt_ctx* c) {
 }
 
 int dopt_phase_metrics_shared(dopt_ctx* c, int include_xnorm, double* out_dev) {
-  if (c && c->sm_C) return no_softmax(__func__);
+  if (c && (c->sm_C || c->sparse)) return no_dense(c, __func__);
   CHECK_ARG(c && out_dev, "NULL argument");
   HIPOK(launch_history(c->dtype, nullptr, c->slab_loss, c->n, c->loss_groups, c->xg[c->gcur], c->ld,
                        (int32_t)c->nchs, include_xnorm != 0, out_dev, c->stream));
@@ -2898,7 +3195,7 @@ int dopt_phase_metrics_shared(dopt_ctx* c, int include_xnorm, double* out_dev) {
 }
 
 int dopt_phase_colsum(dopt_ctx* c, double* sum_dev) {
-  if (c && c->sm_C) return no_softmax(__func__);
+  if (c && (c->sm_C || c->sparse)) return no_dense(c, __func__);
   CHECK_ARG(c && sum_dev, "NULL argument");
   int rc;
   if ((rc = rs_end(c))) return rc;
@@ -2910,7 +3207,7 @@ int dopt_phase_colsum(dopt_ctx* c, double* sum_dev) {
 }
 
 int dopt_phase_xbar(dopt_ctx* c, const double* sum_dev) {
-  if (c && c->sm_C) return no_softmax(__func__);
+  if (c && (c->sm_C || c->sparse)) return no_dense(c, __func__);
   CHECK_ARG(c && sum_dev, "NULL argument");
   HIPOK(launch_colsum_final(c->dtype, sum_dev, 1, n_div(c), c->ld, (int32_t)c->nchs, c->xbar[c->xb ^ 1], nullptr,
                             0.0, 0, c->stream));
@@ -2920,7 +3217,7 @@ int dopt_phase_xbar(dopt_ctx* c, const double* sum_dev) {
 }
 
 int dopt_phase_fold(dopt_ctx* c, double* cons_out, double* xnorm_out, double* loss_out, int slab) {
-  if (c && c->sm_C) return no_softmax(__func__);
+  if (c && (c->sm_C || c->sparse)) return no_dense(c, __func__);
   CHECK_ARG(c, "ctx is NULL");
   CHECK_ARG(slab == 0 || slab == 1, "slab must be 0 or 1");
   if (c->rs_live && !c->rs_sweep) {  // row-space rounds: ||xbar||^2 from the average update's block partials
@@ -2937,7 +3234,7 @@ int dopt_phase_fold(dopt_ctx* c, double* cons_out, double* xnorm_out, double* lo
 // The replicated d-vectors (xbar, Z) take the all-reduced column sums, so every rank holds
 // the same ones; the metric partials are this rank's workers' (folded by dopt_phase_fold).
 int dopt_rs_phase_begin(dopt_ctx* c, int commit, int* ok, uint64_t* hash) {
-  if (c && c->sm_C) return no_softmax(__func__);
+  if (c && (c->sm_C || c->sparse)) return no_dense(c, __func__);
   CHECK_ARG(c && ok && hash, "NULL argument");
   if (!c->have_data) return fail(DOPT_ERR_STATE, "no shards loaded");
   *ok = 0;
@@ -2969,7 +3266,7 @@ int dopt_rs_phase_begin(dopt_ctx* c, int commit, int* ok, uint64_t* hash) {
 
 int dopt_rs_phase_round(dopt_ctx* c, int64_t t, double eta0, double lam_grad, uint32_t metric_flags,
                         double* sum_dev) {
-  if (c && c->sm_C) return no_softmax(__func__);
+  if (c && (c->sm_C || c->sparse)) return no_dense(c, __func__);
   CHECK_ARG(c && sum_dev, "NULL argument");
   if (!c->rs_live) return fail(DOPT_ERR_STATE, "dopt_rs_phase_begin first");
   if (int rc = rs_sweep_closed(c)) return rc;
@@ -2993,7 +3290,7 @@ int dopt_rs_phase_round(dopt_ctx* c, int64_t t, double eta0, double lam_grad, ui
 }
 
 int dopt_rs_phase_pass(dopt_ctx* c, int32_t chunk, int32_t n_chunks, double* sum_dev, int64_t* col_range) {
-  if (c && c->sm_C) return no_softmax(__func__);
+  if (c && (c->sm_C || c->sparse)) return no_dense(c, __func__);
   CHECK_ARG(c && sum_dev && col_range, "NULL argument");
   if (!c->rs_live) return fail(DOPT_ERR_STATE, "dopt_rs_phase_begin first");
   CHECK_ARG(n_chunks >= 1 && chunk >= 0 && chunk < n_chunks, "chunk %d of %d", chunk, n_chunks);
@@ -3017,7 +3314,7 @@ int dopt_rs_phase_pass(dopt_ctx* c, int32_t chunk, int32_t n_chunks, double* sum
 }
 
 int dopt_rs_phase_rows(dopt_ctx* c, int64_t t, double eta0, double lam_grad, uint32_t metric_flags) {
-  if (c && c->sm_C) return no_softmax(__func__);
+  if (c && (c->sm_C || c->sparse)) return no_dense(c, __func__);
   CHECK_ARG(c, "ctx is NULL");
   if (!c->rs_live) return fail(DOPT_ERR_STATE, "dopt_rs_phase_begin first");
   if (int rc = rs_sweep_closed(c)) return rc;
@@ -3034,7 +3331,7 @@ int dopt_rs_phase_rows(dopt_ctx* c, int64_t t, double eta0, double lam_grad, uin
 }
 
 int dopt_rs_phase_cols(dopt_ctx* c, int64_t t, double eta0, double lam_grad, const double* sum_dev) {
-  if (c && c->sm_C) return no_softmax(__func__);
+  if (c && (c->sm_C || c->sparse)) return no_dense(c, __func__);
   CHECK_ARG(c && sum_dev, "NULL argument");
   if (!c->rs_live) return fail(DOPT_ERR_STATE, "dopt_rs_phase_begin first");
   if (int rc = rs_sweep_closed(c)) return rc;
@@ -3053,7 +3350,7 @@ int dopt_rs_phase_cols(dopt_ctx* c, int64_t t, double eta0, double lam_grad, con
 // the chunks of one update in any order, the last one with last = 1.
 int dopt_rs_phase_cols_range(dopt_ctx* c, int64_t t, double eta0, double lam_grad, const double* sum_dev,
                              int64_t c0, int64_t c1, int32_t last) {
-  if (c && c->sm_C) return no_softmax(__func__);
+  if (c && (c->sm_C || c->sparse)) return no_dense(c, __func__);
   CHECK_ARG(c && sum_dev, "NULL argument");
   if (!c->rs_live) return fail(DOPT_ERR_STATE, "dopt_rs_phase_begin first");
   const int dt = c->dtype == DOPT_F32 ? 0 : 1;
@@ -3072,7 +3369,7 @@ int dopt_rs_phase_cols_range(dopt_ctx* c, int64_t t, double eta0, double lam_gra
 }
 
 int dopt_rs_phase_metrics(dopt_ctx* c, uint32_t metric_flags) {
-  if (c && c->sm_C) return no_softmax(__func__);
+  if (c && (c->sm_C || c->sparse)) return no_dense(c, __func__);
   CHECK_ARG(c, "ctx is NULL");
   if (!c->rs_live) return fail(DOPT_ERR_STATE, "dopt_rs_phase_begin first");
   if (int rc = rs_sweep_closed(c)) return rc;
@@ -3089,7 +3386,7 @@ int dopt_rs_phase_metrics(dopt_ctx* c, uint32_t metric_flags) {
 }
 
 int dopt_phase_metrics_pass(dopt_ctx* c, uint32_t flags) {
-  if (c && c->sm_C) return no_softmax(__func__);
+  if (c && (c->sm_C || c->sparse)) return no_dense(c, __func__);
   CHECK_ARG(c, "ctx is NULL");
   if (c->split) {
     int rc;
@@ -3102,7 +3399,7 @@ int dopt_phase_metrics_pass(dopt_ctx* c, uint32_t flags) {
 }
 
 int dopt_phase_metrics(dopt_ctx* c, uint32_t flags, int include_xnorm, double* out_dev) {
-  if (c && c->sm_C) return no_softmax(__func__);
+  if (c && (c->sm_C || c->sparse)) return no_dense(c, __func__);
   CHECK_ARG(c && out_dev, "NULL argument");
   const bool cons = flags & DOPT_RUN_CONSENSUS, loss = flags & DOPT_RUN_OBJECTIVE;
   HIPOK(launch_history(c->dtype, cons ? c->slab_cons : nullptr, loss ? c->slab_loss : nullptr, c->n,
@@ -3120,7 +3417,7 @@ int dopt_phase_metrics(dopt_ctx* c, uint32_t flags, int include_xnorm, double* o
 // collective per round.
 int dopt_lagged_exchange_layout(dopt_ctx* c, int32_t world, int32_t rank, const int64_t* sum_send_row,
                                 const int64_t* sum_recv_row) {
-  if (c && c->sm_C) return no_softmax(__func__);
+  if (c && (c->sm_C || c->sparse)) return no_dense(c, __func__);
   CHECK_ARG(c && sum_send_row && sum_recv_row, "NULL argument");
   CHECK_ARG(world >= 1 && rank >= 0 && rank < world, "bad world / rank");
   CHECK_ARG(world <= 1024, "at most 1024 ranks");
@@ -3241,7 +3538,7 @@ McsArgs lagged_args(dopt_ctx* c, const double* own_in, double* own_out, double* 
 }  // namespace
 
 int dopt_lagged_begin(dopt_ctx* c, int64_t batch) {
-  if (c && c->sm_C) return no_softmax(__func__);
+  if (c && (c->sm_C || c->sparse)) return no_dense(c, __func__);
   CHECK_ARG(c, "ctx is NULL");
   int rc;
   if ((rc = dopt_phase_begin(c, batch))) return rc;
@@ -3351,7 +3648,7 @@ int ipc_pull(dopt_ctx* c) {
 }  // namespace
 
 int dopt_lagged_exchange_issued(dopt_ctx* c, int* ordered) {
-  if (c && c->sm_C) return no_softmax(__func__);
+  if (c && (c->sm_C || c->sparse)) return no_dense(c, __func__);
   CHECK_ARG(c && ordered, "NULL argument");
   *ordered = 0;
   if (!c->lg_side) return DOPT_OK;  // no side stream: the caller orders the engine stream
@@ -3362,7 +3659,7 @@ int dopt_lagged_exchange_issued(dopt_ctx* c, int* ordered) {
 }
 
 int dopt_lagged_transport(dopt_ctx* c, dopt_comm* comm, const int64_t* send_rows, const int64_t* recv_rows) {
-  if (c && c->sm_C) return no_softmax(__func__);
+  if (c && (c->sm_C || c->sparse)) return no_dense(c, __func__);
   CHECK_ARG(c, "ctx is NULL");
   c->xp = nullptr;
   c->xp_ops.clear();
@@ -3398,7 +3695,7 @@ int dopt_lagged_transport(dopt_ctx* c, dopt_comm* comm, const int64_t* send_rows
 }
 
 int dopt_lagged_ipc_export(dopt_ctx* c, uint8_t* mem_handle, uint8_t* event_handle, int64_t* slot_bytes) {
-  if (c && c->sm_C) return no_softmax(__func__);
+  if (c && (c->sm_C || c->sparse)) return no_dense(c, __func__);
   CHECK_ARG(c && mem_handle && event_handle && slot_bytes, "NULL argument");
   if (!c->have_data) return fail(DOPT_ERR_STATE, "load the shards first");
   int rc;
@@ -3434,7 +3731,7 @@ int dopt_lagged_ipc_export(dopt_ctx* c, uint8_t* mem_handle, uint8_t* event_hand
 int dopt_lagged_ipc_import(dopt_ctx* c, int32_t world, int32_t rank, const uint8_t* mem_handles,
                            const uint8_t* event_handles, const int64_t* slot_bytes, const int64_t* src_off,
                            const int64_t* recv_rows, int64_t* counters, double timeout_s) {
-  if (c && c->sm_C) return no_softmax(__func__);
+  if (c && (c->sm_C || c->sparse)) return no_dense(c, __func__);
   CHECK_ARG(c && mem_handles && event_handles && slot_bytes && src_off && recv_rows && counters, "NULL argument");
   CHECK_ARG(c->ipc_send, "dopt_lagged_ipc_export first");
   CHECK_ARG(c->lg_world == world && c->lg_rank == rank,
@@ -3523,7 +3820,7 @@ int dopt_lagged_ipc_import(dopt_ctx* c, int32_t world, int32_t rank, const uint8
 }
 
 int dopt_lagged_ipc_check(dopt_ctx* c, int32_t step) {
-  if (c && c->sm_C) return no_softmax(__func__);
+  if (c && (c->sm_C || c->sparse)) return no_dense(c, __func__);
   CHECK_ARG(c, "ctx is NULL");
   CHECK_ARG(step == 0 || step == 1, "step 0 (publish) or 1 (pull)");
   if (!c->ipc) return fail(DOPT_ERR_STATE, "no pull transport (dopt_lagged_ipc_import first)");
@@ -3535,7 +3832,7 @@ int dopt_lagged_ipc_check(dopt_ctx* c, int32_t step) {
 }
 
 int dopt_lagged_exchange(dopt_ctx* c) {
-  if (c && c->sm_C) return no_softmax(__func__);
+  if (c && (c->sm_C || c->sparse)) return no_dense(c, __func__);
   CHECK_ARG(c, "ctx is NULL");
   int rc;
   if (c->ipc) {
@@ -3554,7 +3851,7 @@ int dopt_lagged_exchange(dopt_ctx* c) {
 }
 
 int dopt_lagged_side_stream(dopt_ctx* c, void* stream) {
-  if (c && c->sm_C) return no_softmax(__func__);
+  if (c && (c->sm_C || c->sparse)) return no_dense(c, __func__);
   CHECK_ARG(c, "ctx is NULL");
   int rc;
   if ((rc = set_device(c))) return rc;
@@ -3567,7 +3864,7 @@ int dopt_lagged_side_stream(dopt_ctx* c, void* stream) {
 
 int dopt_lagged_grad(dopt_ctx* c, int64_t t, double eta0, int64_t batch, const int32_t* idx, double lam_grad,
                      uint32_t metric_flags) {
-  if (c && c->sm_C) return no_softmax(__func__);
+  if (c && (c->sm_C || c->sparse)) return no_dense(c, __func__);
   int rc;
   if ((rc = dopt_phase_set_step(c, t, eta0))) return rc;
   return dopt_phase_grad(c, batch, idx, lam_grad, metric_flags);
@@ -3575,7 +3872,7 @@ int dopt_lagged_grad(dopt_ctx* c, int64_t t, double eta0, int64_t batch, const i
 
 int dopt_lagged_mix(dopt_ctx* c, int64_t t, double eta0, int consensus, double* cons_out, double* xnorm_out,
                     double* loss_out) {
-  if (c && c->sm_C) return no_softmax(__func__);
+  if (c && (c->sm_C || c->sparse)) return no_dense(c, __func__);
   CHECK_ARG(c, "ctx is NULL");
   int rc;
   if ((rc = lagged_ready(c))) return rc;
@@ -3621,7 +3918,7 @@ int dopt_lagged_mix(dopt_ctx* c, int64_t t, double eta0, int consensus, double* 
 
 int dopt_lagged_tail(dopt_ctx* c, int consensus, int objective, double* cons1, double* xnorm1, double* loss1,
                      double* cons2, double* xnorm2, double* loss2) {
-  if (c && c->sm_C) return no_softmax(__func__);
+  if (c && (c->sm_C || c->sparse)) return no_dense(c, __func__);
   CHECK_ARG(c, "ctx is NULL");
   int rc;
   if ((rc = lagged_ready(c))) return rc;

@@ -1,0 +1,11 @@
+// sparse_f64.hip -- k_round_sparse instantiations: float64 iterates and arithmetic over float64-stored non-zeros.
+#include "kcommon.h"
+#include "k_round_sparse.inc"
+
+namespace dopt {
+
+hipError_t launch_sparse_f64(int problem, const SparseArgs& a, int n_workers, hipStream_t s) {
+  return sparse_dispatch<double, double>(problem, a, n_workers, s);
+}
+
+}  // namespace dopt

@@ -43,6 +43,11 @@ Config keys beyond the reference's (all optional):
              objective over the shards' own rows
   num_classes    problem_type='softmax', required: an int in [2, 16]
 
+Sparse shards: when every worker's X_local is a scipy.sparse matrix, DecentralizedTrainer.run keeps the
+shards in CSR on the device (Engine.load_shards_csr) and runs the sparse round kernel: algorithm='dsgd',
+'logistic' / 'quadratic', single process, CSR mixing, sampling 'legacy' or 'full', no checkpoints, the
+objective over the shards' own rows (X_full, sparse or dense, must be their union in worker order).
+
 Multi-process mode: when torch.distributed is initialised with more than one rank
 (e.g. `python -m torch.distributed.run --nproc-per-node 8 main.py`), every rank
 keeps all Worker objects (same data, same RNG stream) but loads only its
@@ -119,6 +124,42 @@ def _pack(workers, n_features, f32=False):
         y = np.concatenate([np.asarray(w.y_local, dtype=dt).reshape(-1) for w in workers])
     else:
         X, y = np.zeros((0, n_features), dtype=dt), np.zeros(0, dtype=dt)
+    return X, y, off
+
+
+def _is_sparse(X):
+    return hasattr(X, "tocsr") and not isinstance(X, np.ndarray)  # scipy.sparse matrices and arrays
+
+
+def _sparse_workers(workers):
+    """True when every worker's X_local is a scipy.sparse matrix, False when none is."""
+    kinds = {_is_sparse(w.X_local) for w in workers}
+    if len(kinds) > 1:
+        raise ValueError("workers with sparse and dense X_local in one trainer: give every shard as scipy.sparse, "
+                         "or none")
+    return kinds == {True}
+
+
+def _pack_csr(workers, n_features):
+    """The shards as one CSR matrix over the global rows (sorted column indices, duplicates summed), the
+    labels and the row offsets."""
+    import scipy.sparse as sp
+
+    mats = []
+    for w in workers:
+        A = w.X_local.tocsr()
+        if A.shape[1] != n_features:
+            raise ValueError(f"worker {w.worker_id}: X_local has {A.shape[1]} columns, n_features = {n_features}")
+        if not A.has_canonical_format:
+            A = A.copy()
+            A.sum_duplicates()
+        mats.append(A)
+    f32 = all(A.dtype == np.float32 for A in mats) and all(np.asarray(w.y_local).dtype == np.float32 for w in workers)
+    dt = np.float32 if f32 else np.float64
+    off = np.zeros(len(workers) + 1, dtype=np.int64)
+    np.cumsum([A.shape[0] for A in mats], out=off[1:])
+    X = sp.vstack(mats, format="csr", dtype=dt) if mats and off[-1] > 0 else sp.csr_matrix((0, n_features), dtype=dt)
+    y = np.concatenate([np.asarray(w.y_local, dtype=dt).reshape(-1) for w in workers]) if mats else np.zeros(0, dt)
     return X, y, off
 
 
@@ -559,6 +600,8 @@ class CentralizedTrainer:
         start_time = time.time()
         if self.config["problem_type"] == "softmax":
             raise NotImplementedError("softmax regression runs decentralized (DecentralizedTrainer, algorithm='dsgd')")
+        if _sparse_workers(self.workers):
+            raise NotImplementedError("sparse shards run decentralized (DecentralizedTrainer, algorithm='dsgd')")
         self._get_objective_func()
         reg_param = self._get_regularization_param()
         self.total_floats_transmitted = 0
@@ -682,6 +725,8 @@ class DecentralizedTrainer:
 
     def run(self, n_iterations, X_full=None, y_full=None, f_opt=0.0):
         start_time = time.time()
+        if _sparse_workers(self.workers):
+            return self._run_sparse(int(n_iterations), X_full, y_full, f_opt, start_time)
         if self.config["problem_type"] == "softmax":
             return self._run_softmax(int(n_iterations), X_full, y_full, f_opt, start_time)
         self._get_objective_func()
@@ -895,6 +940,78 @@ class DecentralizedTrainer:
                 self.total_floats_transmitted += n * iteration_transmission
         self.loop_seconds = time.perf_counter() - loop_start
         models = eng.softmax_get_models()
+        for i, worker in enumerate(self.workers):
+            worker.x = models[i]
+        _warn_nonfinite(self.history, self.config)
+        print(f"Decentralized ({self.topology}) training finished. Time: {time.time() - start_time:.2f}s")
+        return self.history, np.mean(models, axis=0)
+
+    def _run_sparse(self, T, X_full, y_full, f_opt, start_time):
+        """Every worker's X_local is a scipy.sparse matrix: the rounds of Engine.run_sparse (D-SGD over CSR
+        shards, one launch of the sparse round kernel per round) in D-SGD's chunk loop.  Every unsupported
+        combination is refused before any device call."""
+        cfg = self.config
+        if cfg["problem_type"] not in ("logistic", "quadratic"):
+            raise NotImplementedError(f"sparse shards run 'logistic' or 'quadratic', not {cfg['problem_type']!r}")
+        if cfg.get("algorithm", "dsgd") != "dsgd":
+            raise NotImplementedError(f"sparse shards run algorithm='dsgd', not {cfg.get('algorithm')!r}")
+        if _dist_info(cfg) is not None:
+            raise NotImplementedError("sparse shards run in a single process (no multi-rank job)")
+        if self._mean_mixing() and self._topo.uniform_offdiag() is not None:
+            raise NotImplementedError("sparse shards mix through the CSR matrix: raise 'mean_mixing_min' above the "
+                                      "number of workers")
+        ck_keys = [k for k in ("checkpoint_path", "checkpoint_every", "resume_from") if cfg.get(k)]
+        if ck_keys:
+            raise NotImplementedError(f"sparse shards do not checkpoint (config {ck_keys})")
+        if cfg.get("sampling", "legacy") not in ("legacy", "full"):
+            raise NotImplementedError("sparse shards draw their minibatches on the host (sampling='legacy' or 'full')")
+        d = self.n_features
+        X, y, off = _pack_csr(self.workers, d)
+        want_obj = X_full is not None and y_full is not None
+        if want_obj:
+            same = tuple(X_full.shape) == X.shape and np.array_equal(np.asarray(y_full, dtype=np.float64).reshape(-1), y)
+            if same and _is_sparse(X_full):
+                same = (X_full.tocsr() != X).nnz == 0
+            elif same:
+                same = np.array_equal(np.asarray(X_full), X.toarray())
+            if not same:
+                raise NotImplementedError("sparse shards take their objective over their own rows: X_full must be "
+                                          "the shards' rows in worker order")
+        self.total_floats_transmitted = 0
+        reg_param = self._get_regularization_param()
+        lam_grad = _grad_reg(cfg, T, self.workers)
+        dev, dtype = _device(cfg), cfg.get("dtype", "float64")
+        xdt = _data_dtype(cfg, d, [X.data, y])
+        key = ("csr", cfg["problem_type"], xdt, d, _fingerprint([X.indptr, X.indices, X.data, y, off],
+                                                                  _sampled_key(cfg)))
+        eng = _ENGINES.get((dev, dtype))
+        if eng is None or eng.data_key != key:
+            if eng is not None:
+                _ENGINES.pop((dev, dtype)).close()  # free the previous data set's HBM
+            eng = _dopt.Engine(dev, dtype, data_dtype=xdt)
+            eng.load_shards_csr(cfg["problem_type"], X.indptr, X.indices, X.data, y, off, d)
+            eng.obj_key = None
+            eng.data_key = key
+            _ENGINES[(dev, dtype)] = eng
+        eng.set_sampler("host", seed=0, first_worker=0)
+        t = self._topo
+        eng.set_topology(t.row_ptr, t.col, t.w)
+        eng.set_models(np.stack([np.asarray(w.x, dtype=np.float64).reshape(d) for w in self.workers]))
+        iteration_transmission = np.sum(self.degrees) * d
+        eta0 = cfg["learning_rate_eta0"]
+        loop_start = time.perf_counter()
+        with closing(_index_chunks(self.workers, T, cfg)) as chunks:
+            for t0, n, b, idx, _ in chunks:
+                t_host = time.time() - start_time
+                obj, cons, tim = eng.run_sparse(n, eta0, b, lam_grad, reg_param, f_opt, idx=idx, t0=t0,
+                                                objective=want_obj, consensus=True, want_time=True)
+                self.history["consensus_error"].extend(list(cons))
+                if want_obj:
+                    self.history["objective"].extend(list(obj))
+                self.history["time"].extend((tim + t_host).tolist())
+                self.total_floats_transmitted += n * iteration_transmission
+        self.loop_seconds = time.perf_counter() - loop_start
+        models = eng.get_models()
         for i, worker in enumerate(self.workers):
             worker.x = models[i]
         _warn_nonfinite(self.history, self.config)

@@ -59,7 +59,8 @@ extern "C" {
  *      Added under 9 (additions only, nothing changed): gradient tracking -- dopt_run_gt,
  *      dopt_gt_set_state, dopt_gt_get_state; CHOCO-SGD -- dopt_run_choco, dopt_choco_set_state,
  *      dopt_choco_get_state; softmax regression -- DOPT_SOFTMAX, dopt_load_shards_softmax,
- *      dopt_run_softmax, dopt_softmax_set_models, dopt_softmax_get_models. */
+ *      dopt_run_softmax, dopt_softmax_set_models, dopt_softmax_get_models; sparse (CSR) shards --
+ *      dopt_load_shards_csr, dopt_run_sparse. */
 #define DOPT_ABI_VERSION 9
 
 typedef struct dopt_ctx dopt_ctx;
@@ -289,6 +290,36 @@ int dopt_run_softmax(dopt_ctx *ctx, int64_t t0, int64_t T, double eta0, int64_t 
 /* Iterates of a softmax context, N x C x d row-major float64 at the boundary (NULL x: zeros). */
 int dopt_softmax_set_models(dopt_ctx *ctx, const double *x);
 int dopt_softmax_get_models(dopt_ctx *ctx, double *x);
+
+/* Sparse shards: D-SGD for DOPT_LOGISTIC / DOPT_QUADRATIC over shards given in CSR, for data whose
+ * dense form does not fit (bag-of-words features).  row_ptr ([n_rows + 1], n_rows =
+ * shard_offsets[n_workers]) runs over the global rows, worker i owning rows [shard_offsets[i],
+ * shard_offsets[i + 1]); col (int32) and val hold the non-zeros, val and y float64 or -- src_f32 --
+ * float32, stored as dopt_set_data_dtype says.  Checked on the host (DOPT_ERR_INVALID): row_ptr
+ * monotone from 0, and within each row columns strictly ascending (so no duplicates) inside [0, d).
+ * The call also builds the column view of every shard (the same non-zeros sorted by column, only the
+ * columns the shard touches), zeroes the iterates and makes the context a SPARSE context.  Limits
+ * (DOPT_ERR_UNSUPPORTED): d <= 2^20, shards of at most 16384 rows and fewer than 2^31 non-zeros.
+ * On a sparse context dopt_set_models / _get_models / _zero_models and dopt_set_topology work,
+ * dopt_get_shard returns the densified shard, and only dopt_run_sparse computes gradients or
+ * objectives: every entry point dopt_load_shards_softmax's comment lists -- except the model
+ * accessors -- and dopt_run_softmax return DOPT_ERR_UNSUPPORTED.  Loading or generating other shards
+ * makes it an ordinary context again. */
+int dopt_load_shards_csr(dopt_ctx *ctx, int problem, int64_t n_workers, int64_t d,
+                         const int64_t *shard_offsets, const int64_t *row_ptr, const int32_t *col,
+                         const void *val, const void *y, int src_f32);
+
+/* T rounds of D-SGD over the CSR shards, rounds t0..t0+T-1; parameters, outputs and schedule as
+ * dopt_run_gt: one launch of the sparse round kernel per round (formulas, eta_t and the empty-shard
+ * rule of dopt_run_dsgd), the column sums of the new iterates with the history row of the previous
+ * round folded in; with minibatch indices DOPT_RUN_OBJECTIVE takes one more launch of the same
+ * kernel per history row (every row of every shard).  The rows of a minibatch must be distinct, as
+ * the host sampler draws them.  A run split into several calls gives the bits of one call, and two
+ * runs give the same bits.  CSR mixing (dopt_set_topology) on one device only; idx == NULL needs
+ * full-shard batches (no device sampler).  DOPT_ERR_STATE on a context that is not sparse. */
+int dopt_run_sparse(dopt_ctx *ctx, int64_t t0, int64_t T, double eta0, int64_t batch,
+                    const int32_t *idx, double lam_grad, double lam_obj, double f_opt,
+                    uint32_t flags, double *obj_out, double *cons_out, double *time_out);
 
 /* Tracker state of dopt_run_gt, N x d row-major float64 at the boundary like the iterates:
  * y = the trackers, g = every worker's last stochastic gradient.  A NULL argument of
