@@ -65,6 +65,7 @@ _SIGS = {
     "dopt_run_dsgd_pipelined": ([_P, _I64, _I64, _D, _I64, _P, _D, _D, _D, ctypes.c_uint32, _P, _P, _P, _P],
                                 ctypes.c_int),
     "dopt_run_gt": ([_P, _I64, _I64, _D, _I64, _P, _D, _D, _D, ctypes.c_uint32, _P, _P, _P], ctypes.c_int),
+    "dopt_run_local": ([_P, _I64, _I64, _D, _I64, _P, _D, _D, _D, ctypes.c_uint32, _I64, _P, _P, _P], ctypes.c_int),
     "dopt_gt_set_state": ([_P, _P, _P], ctypes.c_int),
     "dopt_gt_get_state": ([_P, _P, _P], ctypes.c_int),
     "dopt_run_choco": ([_P, _I64, _I64, _D, _I64, _P, _D, _D, _D, ctypes.c_uint32, _I64, _D, _P, _P, _P], ctypes.c_int),
@@ -488,6 +489,26 @@ class Engine:
         flags = (RUN_OBJECTIVE if objective else 0) | (RUN_CONSENSUS if consensus else 0)
         check(lib().dopt_run_gt(self._h, int(t0), T, float(eta0), int(batch), _ptr(idx), float(lam_grad),
                                 float(lam_obj), float(f_opt), flags, _ptr(obj), _ptr(cons), _ptr(tim)))
+        return obj, cons, tim
+
+    def run_local(self, T, eta0, batch, lam_grad, lam_obj, local_steps, f_opt=0.0, idx=None, t0=0,
+                  objective=True, consensus=True, want_time=True):
+        """dopt_run_local: T communication rounds of local_steps gradient steps each (one fused launch
+        per round); idx: [T * local_steps, N, batch] draws (mt_choice_rounds(T * local_steps, ..)) or
+        None for full-shard batches; t0 counts rounds.  Return value as run_dsgd, one entry per round."""
+        T = int(T)
+        obj = np.zeros(T) if objective else None
+        cons = np.zeros(T) if consensus else None
+        tim = np.zeros(T) if want_time else None
+        if idx is not None:
+            idx = np.ascontiguousarray(idx, dtype=np.int32)
+            if idx.ndim != 3 or idx.shape[0] != T * int(local_steps) or idx.shape[2] != int(batch):
+                raise ValueError(f"idx of shape (T * local_steps, N, batch) = ({T * int(local_steps)}, N, {int(batch)}) "
+                                 f"expected, got {idx.shape}")
+        flags = (RUN_OBJECTIVE if objective else 0) | (RUN_CONSENSUS if consensus else 0)
+        check(lib().dopt_run_local(self._h, int(t0), T, float(eta0), int(batch), _ptr(idx), float(lam_grad),
+                                   float(lam_obj), float(f_opt), flags, int(local_steps), _ptr(obj), _ptr(cons),
+                                   _ptr(tim)))
         return obj, cons, tim
 
     def run_sparse(self, T, eta0, batch, lam_grad, lam_obj, f_opt=0.0, idx=None, t0=0,

@@ -256,6 +256,25 @@ hipError_t launch_gt_f32(int problem, int cpl, bool met, const GtArgs& a, int n_
 hipError_t launch_gt_f64(int problem, int cpl, bool met, const GtArgs& a, int n_workers, hipStream_t s);
 hipError_t launch_gt_x32(int problem, int cpl, bool met, const GtArgs& a, int n_workers, hipStream_t s);
 
+// ---- local steps (k_round_local.inc): tau gradient steps per gossip round in one launch, one
+// workgroup per worker
+//   u = sum_j W_ij x_j - eta[0] g_i(x_i),   u <- u - eta[k] g_i(u)  (k = 1 .. tau - 1),   x_new_i = u
+// r: the D-SGD round's arguments; r.idx: this round's [tau x n x b] draws (step k's batch of worker i
+// at (k n + i) b), or null (all rows); r.eta is unused.  r.flags: F_STEP (without it the launch only
+// takes the metrics of x_old at xbar), F_CONS, and -- full-shard batches only -- F_LOSS, both taken
+// in step 0's pass.  No halo rows, no F_MEAN.
+constexpr int kMaxLocalSteps = 64;  // DOPT_MAX_LOCAL_STEPS (dopt.h)
+struct LocalArgs {
+  RoundArgs r;
+  int32_t tau;                 // gradient steps of the round, 1 <= tau <= kMaxLocalSteps
+  int32_t prefetch;            // A/B: step k + 1's first row requested before step k's reduction barrier (same bits)
+  double eta[kMaxLocalSteps];  // eta0 / sqrt(s + 1) of the round's global steps s = tau t + k
+};
+// per element-type pair (local_f32.hip / local_f64.hip / local_x32.hip); cpl = 16-byte DATA chunks per lane
+hipError_t launch_local_f32(int problem, int cpl, bool met, const LocalArgs& a, int n_workers, hipStream_t s);
+hipError_t launch_local_f64(int problem, int cpl, bool met, const LocalArgs& a, int n_workers, hipStream_t s);
+hipError_t launch_local_x32(int problem, int cpl, bool met, const LocalArgs& a, int n_workers, hipStream_t s);
+
 // ---- CHOCO-SGD (k_round_choco.inc): top-k compressed gossip with error feedback, one launch per
 // round, one workgroup per worker
 //   x_new_i = x_i - eta g_i + gamma (sum_j W_ij xhat_j - xhat_i),   xhat_i <- xhat_i + top_k(x_new_i - xhat_i)

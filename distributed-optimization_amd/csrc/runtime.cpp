@@ -2123,6 +2123,127 @@ int dopt_gt_get_state(dopt_ctx* c, double* y, double* g) {
   return DOPT_OK;
 }
 
+// ---------------------------------------------------------------------------- local steps
+namespace {
+
+static_assert(kMaxLocalSteps == DOPT_MAX_LOCAL_STEPS, "dopt.h and engine.h disagree");
+
+hipError_t launch_local(dopt_ctx* c, bool met, const LocalArgs& g) {
+  if (c->dtype == DOPT_F32) return launch_local_f32(c->problem, c->cpl, met, g, (int)c->n, c->stream);
+  if (c->xdtype == DOPT_F32) return launch_local_x32(c->problem, c->cpl, met, g, (int)c->n, c->stream);
+  return launch_local_f64(c->problem, c->cpl, met, g, (int)c->n, c->stream);
+}
+
+// T communication rounds of tau gradient steps each on run_gt's schedule: k_round_local, then the
+// column sums of the new iterates with the history row of the previous round folded in.  Round h's
+// launch takes the metrics of x_h at xbar_h (history[h - 1]) in its step-0 pass; the row of the last
+// iterates takes one more launch of the same kernel without the step.  Host minibatches (idx:
+// [T tau][n][b], uploaded in chunks of whole rounds) and a separate objective dataset: the kernel
+// fuses the consensus only and the objective takes the metrics-only pass after every round.
+int run_local(dopt_ctx* c, int64_t t0, int64_t T, double eta0, int64_t batch, const int32_t* idx, double lam_grad,
+              double lam_obj, double f_opt, uint32_t flags, int64_t tau, double* obj_out, double* cons_out,
+              double* time_out) {
+  CHECK_ARG(c, "ctx is NULL");
+  CHECK_ARG(tau >= 1 && tau <= kMaxLocalSteps, "local_steps must be in [1, 64]");
+  if (!c->have_data) return fail(DOPT_ERR_STATE, "no shards loaded");
+  if (c->split)
+    return fail(DOPT_ERR_UNSUPPORTED, "local steps: rows of %lld elements are column-blocked; the local-steps round "
+                "holds a row per wave (at most %d 16-byte chunks per lane)", (long long)c->d,
+                max_chunks_per_lane(c->dtype, c->xdtype));
+  if (!c->have_topo) return fail(DOPT_ERR_STATE, "no topology set");
+  if (c->mean_mix)
+    return fail(DOPT_ERR_UNSUPPORTED, "local steps: mean mixing (dopt_set_mixing_mean) is not supported; give the "
+                "complete graph as CSR (dopt_set_topology)");
+  if (c->n_halo > 0 || c->n_send > 0 || c->sptr)
+    return fail(DOPT_ERR_UNSUPPORTED, "local steps: contexts with a halo plan (multi-GPU slices) are not supported");
+  if (!idx && batch < c->max_m && c->sampler == DOPT_SAMPLE_DEVICE)
+    return fail(DOPT_ERR_UNSUPPORTED, "local steps: the device sampler is not supported; pass idx");
+  int rc;
+  if ((rc = check_run(c, T, batch, idx, true))) return rc;
+  if ((rc = set_device(c))) return rc;
+  if ((rc = rs_end(c))) return rc;
+  c->carry_pending = false;
+  c->send_fresh = false;
+  if (T == 0) return DOPT_OK;
+  if ((rc = ensure_hist(c, T + 1))) return rc;
+  const bool want_obj = flags & DOPT_RUN_OBJECTIVE, want_cons = flags & DOPT_RUN_CONSENSUS;
+  const bool metrics = want_obj || want_cons;
+  const bool fuse_loss = want_obj && !idx && !c->obj_sep;  // step 0's pass walks every objective row
+  const bool pass_loss = want_obj && !fuse_loss;
+  // A/B knob, read per call: 0 = step k + 1's first row requested after step k's reload instead of
+  // before its reduction barrier (same bits)
+  const char* pre_env = getenv("DOPT_LOCAL_PREFETCH");
+  const bool prefetch = !pre_env || atoi(pre_env) != 0;
+  const int64_t bt = batch * tau;  // index columns of a round: tau draws of `batch` per worker
+  const int64_t CH = idx ? idx_chunk_rounds(c, T, bt) : 1;
+  int& xb = c->xb;
+  if ((rc = colsum_current(c))) return rc;  // xbar of the starting iterates
+  HIPOK(launch_stamp(c->stamps, c->stream));
+
+  auto local_args = [&](bool step, bool met) {
+    LocalArgs g;
+    memset(&g, 0, sizeof(g));
+    g.r = base_args(c);
+    g.r.x_old = c->xs[c->cur];
+    g.r.x_new = c->xs[c->cur ^ 1];
+    g.r.xbar = c->xbar[xb];
+    g.r.lam = lam_grad;
+    g.r.b = batch;
+    g.r.flags |= (step ? F_STEP : 0) | (met && want_cons ? F_CONS : 0) | (met && fuse_loss ? F_LOSS : 0);
+    g.tau = (int32_t)tau;
+    g.prefetch = prefetch ? 1 : 0;
+    if (g.r.flags & F_LOSS) c->loss_groups = c->n;  // per-worker loss slabs
+    return g;
+  };
+  // history row `row` = the slabs of the current launch (and, pass_loss, of the last metrics pass) at xbar[xb]
+  auto fold_args = [&](int64_t row) {
+    double* hr = c->hraw + 3 * row;
+    return FoldArgs{want_cons ? c->slab_cons : nullptr, c->n, want_obj ? c->slab_loss : nullptr, c->loss_groups,
+                    want_obj ? c->xbar[xb] : nullptr, hr, hr + 1, hr + 2};
+  };
+
+  for (int64_t h = 0; h < T; ++h) {
+    const int64_t t = t0 + h;
+    if (idx && h % CH == 0) {
+      if ((rc = upload_idx_chunk(c, idx, h, std::min(CH, T - h), bt))) return rc;
+    }
+    const bool met = metrics && h > 0;
+    LocalArgs g = local_args(true, met);
+    g.r.idx = idx ? c->idx + (h % CH) * c->n * bt : nullptr;
+    for (int64_t k = 0; k < tau; ++k) g.eta[k] = eta0 / sqrt((double)(tau * t + k + 1));  // trainer.py:138-140
+    if (c->prof && (rc = prof_event(c, false))) return rc;
+    HIPOK(launch_local(c, metrics, g));
+    if (c->prof && (rc = prof_event(c, true))) return rc;
+    // xbar of the round's iterates and the stamp of the round's end; history[h - 1] rides the launch
+    const FoldArgs fold = fold_args(met ? h - 1 : 0);
+    HIPOK(launch_colsum(c->dtype, c->xs[c->cur ^ 1], c->n, c->ld, (int32_t)c->nchs, kRowsPerGroup, c->part,
+                        c->stamps + h + 1, n_div(c), c->xbar[xb ^ 1], nullptr, 0.0, 0, c->stream, c->S,
+                        met ? &fold : nullptr));
+    if (pass_loss && (rc = metrics_pass(c, c->xs[c->cur ^ 1], c->xbar[xb ^ 1], false, false, true))) return rc;
+    c->cur ^= 1;
+    xb ^= 1;
+  }
+  if (metrics) {  // the row of the last iterates; the column sums land in the spare xbar
+    const LocalArgs g = local_args(false, true);
+    if (want_cons || fuse_loss) HIPOK(launch_local(c, true, g));
+    const FoldArgs fold = fold_args(T - 1);
+    HIPOK(launch_colsum(c->dtype, c->xs[c->cur], c->n, c->ld, (int32_t)c->nchs, kRowsPerGroup, c->part, nullptr,
+                        n_div(c), c->xbar[xb ^ 1], nullptr, 0.0, 0, c->stream, c->S, &fold));
+  }
+  return finish_run(c, T, T, lam_obj, f_opt, want_obj ? obj_out : nullptr, want_cons ? cons_out : nullptr,
+                    time_out);
+}
+
+}  // namespace
+
+int dopt_run_local(dopt_ctx* c, int64_t t0, int64_t T, double eta0, int64_t batch, const int32_t* idx,
+                   double lam_grad, double lam_obj, double f_opt, uint32_t flags, int64_t local_steps, double* obj_out,
+                   double* cons_out, double* time_out) {
+  if (c && (c->sm_C || c->sparse)) return no_dense(c, __func__);
+  return run_local(c, t0, T, eta0, batch, idx, lam_grad, lam_obj, f_opt, flags, local_steps, obj_out, cons_out,
+                   time_out);
+}
+
 // ---------------------------------------------------------------------------- CHOCO-SGD
 namespace {
 

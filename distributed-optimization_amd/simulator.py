@@ -86,7 +86,9 @@ class Simulator:
     def run_all(self):
         c = self.config
         print(f"\n=== Starting Simulation: {c['problem_type']} ===")
-        self._run_one("Centralized", lambda: CentralizedTrainer(self.workers, self.n_features, c))
+        # 'local_steps' is a knob of the decentralized rounds: the centralized baseline takes one step per round
+        central = {k: v for k, v in c.items() if k != "local_steps"} if "local_steps" in c else c
+        self._run_one("Centralized", lambda: CentralizedTrainer(self.workers, self.n_features, central))
         self._run_one("D-SGD (Ring)", lambda: DecentralizedTrainer(self.workers, "ring", self.n_features, c))
         n = c["n_workers"]
         if int(np.sqrt(n)) ** 2 == n and n > 0:

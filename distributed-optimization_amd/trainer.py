@@ -36,6 +36,15 @@ Config keys beyond the reference's (all optional):
   compression_k  algorithm='choco', required: entries sent per worker and round, an int in
              [1, n_features]
   choco_gamma    algorithm='choco', required: the consensus step size, a float in (0, 1]
+  local_steps    DecentralizedTrainer, algorithm='dsgd', dense 'logistic' / 'quadratic' workers: an
+             int in [1, 64] (default 1), the gradient steps every worker takes on its own shard per
+             gossip round (Local SGD / periodic decentralized SGD: x_{s+1} = W_s x_s - eta_s g_s,
+             W_s = W when s is a multiple of local_steps, else I; eta_s = eta0 / sqrt(s + 1)).
+             Above 1, run(n_iterations) runs n_iterations COMMUNICATION rounds of local_steps
+             steps -- one fused launch each -- the histories have one entry per round and
+             total_floats_transmitted grows by sum(degrees) * d per round; the legacy RNG stream
+             advances as n_iterations * local_steps D-SGD rounds would.  Single process, CSR
+             mixing, host sampling; checkpoint / resume keys raise NotImplementedError
   problem_type   'logistic' / 'quadratic' (the reference's), or 'softmax': multinomial logistic
              regression with labels in {0 .. num_classes - 1} and iterates of shape
              (num_classes, n_features); DecentralizedTrainer with algorithm='dsgd' only, one
@@ -69,6 +78,7 @@ DENSE_LIMIT = 4096          # dense adj / W attributes up to this many workers
 MEAN_MIX_MIN = 128          # complete graphs from this size mix through the column sums
 ROW_RESIDENT_MAX = 2048     # longer float64 rows take the column-blocked rounds (complete graphs: the
                             # row-space rounds, DESIGN.md 6c, which mix through the column sums)
+MAX_LOCAL_STEPS = 64        # dopt.h DOPT_MAX_LOCAL_STEPS: the round's step sizes travel in the launch arguments
 SOFTMAX_MAX_CLASSES = 16    # the softmax round pads the classes to one 16-column matrix tile
 IDX_CHUNK_ELEMS = 1 << 24   # host index buffer per device call (64 MiB of int32)
 IDX_CHUNK_ROUNDS = 512      # rounds per device call when indices are drawn (the next chunk's draw
@@ -395,6 +405,14 @@ def _grad_reg(cfg, n_iterations, workers):
     return lam if cfg["problem_type"] in ("logistic", "softmax") else mu
 
 
+def _local_steps(cfg):
+    """config 'local_steps': gradient steps per gossip round, an int in [1, MAX_LOCAL_STEPS] (default 1)."""
+    tau = cfg.get("local_steps", 1)
+    if isinstance(tau, bool) or not isinstance(tau, (int, np.integer)) or not 1 <= tau <= MAX_LOCAL_STEPS:
+        raise ValueError(f"config 'local_steps' is an int in [1, {MAX_LOCAL_STEPS}]: got {tau!r}")
+    return int(tau)
+
+
 def _batch_size(workers):
     bs = {int(w.batch_size) for w in workers}
     if len(bs) > 1:
@@ -598,6 +616,8 @@ class CentralizedTrainer:
     def run(self, n_iterations, X_full=None, y_full=None, f_opt=0.0):
         print("\n--- Running Centralized Synchronous mini-batch SGD ---")
         start_time = time.time()
+        if _local_steps(self.config) != 1:
+            raise NotImplementedError("local steps run decentralized (DecentralizedTrainer, algorithm='dsgd')")
         if self.config["problem_type"] == "softmax":
             raise NotImplementedError("softmax regression runs decentralized (DecentralizedTrainer, algorithm='dsgd')")
         if _sparse_workers(self.workers):
@@ -725,6 +745,9 @@ class DecentralizedTrainer:
 
     def run(self, n_iterations, X_full=None, y_full=None, f_opt=0.0):
         start_time = time.time()
+        tau = _local_steps(self.config)
+        if tau != 1:
+            return self._run_local_steps(tau, int(n_iterations), X_full, y_full, f_opt, start_time)
         if _sparse_workers(self.workers):
             return self._run_sparse(int(n_iterations), X_full, y_full, f_opt, start_time)
         if self.config["problem_type"] == "softmax":
@@ -829,6 +852,72 @@ class DecentralizedTrainer:
                 self.history["time"].extend((tim + t_host).tolist())
                 for _ in range(n):
                     self.total_floats_transmitted += iteration_transmission
+        self.loop_seconds = time.perf_counter() - loop_start
+        models = eng.get_models()
+        for i, worker in enumerate(self.workers):
+            worker.x = models[i, :]
+        _warn_nonfinite(self.history, self.config)
+        print(f"Decentralized ({self.topology}) training finished. Time: {time.time() - start_time:.2f}s")
+        final_avg_model = np.mean([worker.x for worker in self.workers], axis=0)
+        return self.history, final_avg_model
+
+    def _run_local_steps(self, tau, T, X_full, y_full, f_opt, start_time):
+        """config 'local_steps' = tau > 1: T communication rounds of tau gradient steps, the rounds of
+        Engine.run_local.  Chunks of whole rounds: a chunk of n rounds draws n * tau rounds of D-SGD
+        minibatches (mt_choice_rounds; full-shard batches advance the stream without making indices),
+        so the legacy stream ends where T * tau D-SGD rounds would leave it.  Every unsupported
+        combination is refused before any device call."""
+        cfg = self.config
+        if _sparse_workers(self.workers):
+            raise NotImplementedError("local steps run on dense shards (sparse shards: local_steps = 1)")
+        if cfg["problem_type"] == "softmax":
+            raise NotImplementedError("local steps run 'logistic' or 'quadratic' (softmax: local_steps = 1)")
+        if cfg.get("algorithm", "dsgd") != "dsgd":
+            raise NotImplementedError(f"local steps run algorithm='dsgd', not {cfg.get('algorithm')!r}")
+        self._get_objective_func()
+        reg_param = self._get_regularization_param()
+        self.total_floats_transmitted = 0
+        lam_grad = _grad_reg(cfg, T, self.workers)
+        if _dist_info(cfg) is not None:
+            raise NotImplementedError("local steps run in a single process (no multi-rank job)")
+        if self._mean_mixing() and self._topo.uniform_offdiag() is not None:
+            raise NotImplementedError("local steps mix through the CSR matrix: raise 'mean_mixing_min' above the "
+                                      "number of workers")
+        ck_keys = [k for k in ("checkpoint_path", "checkpoint_every", "resume_from") if cfg.get(k)]
+        if ck_keys:
+            raise NotImplementedError(f"local steps do not checkpoint (config {ck_keys})")
+        mode = cfg.get("sampling", "legacy")
+        if mode == "device":
+            raise NotImplementedError("local steps draw their minibatches on the host (sampling='legacy')")
+        eng = _engine(self.workers, self.n_features, cfg, X_full=X_full, y_full=y_full)
+        want_obj = _set_objective_data(eng, self.workers, self.n_features, X_full, y_full, _sampled_key(cfg))
+        t = self._topo
+        eng.set_topology(t.row_ptr, t.col, t.w)
+        eng.set_models(np.stack([np.asarray(w.x, dtype=np.float64) for w in self.workers]))
+        iteration_transmission = np.sum(self.degrees) * self.n_features  # one gossip step per round
+        eta0 = cfg["learning_rate_eta0"]
+        b = _batch_size(self.workers)
+        rows = np.array([w.n_local_samples for w in self.workers], dtype=np.int64)
+        full = b >= (rows.max() if len(rows) else 0)
+        per_round = tau * max(1, len(self.workers) * (1 if full else b))
+        chunk = max(1, min(IDX_CHUNK_ROUNDS // tau, IDX_CHUNK_ELEMS // per_round))
+        loop_start = time.perf_counter()
+        for t0 in range(0, T, chunk):
+            n = min(chunk, T - t0)
+            idx = None
+            if not full:
+                idx = _dopt.mt_choice_rounds(n * tau, rows, b)
+            elif mode != "full":
+                _dopt.mt_advance_rounds(n * tau, rows)
+            t_host = time.time() - start_time
+            obj, cons, tim = eng.run_local(n, eta0, b, lam_grad, reg_param, tau, f_opt, idx=idx, t0=t0,
+                                           objective=want_obj, consensus=True, want_time=True)
+            self.history["consensus_error"].extend(list(cons))
+            if want_obj:
+                self.history["objective"].extend(list(obj))
+            self.history["time"].extend((tim + t_host).tolist())
+            for _ in range(n):
+                self.total_floats_transmitted += iteration_transmission
         self.loop_seconds = time.perf_counter() - loop_start
         models = eng.get_models()
         for i, worker in enumerate(self.workers):

@@ -60,7 +60,8 @@ extern "C" {
  *      dopt_gt_set_state, dopt_gt_get_state; CHOCO-SGD -- dopt_run_choco, dopt_choco_set_state,
  *      dopt_choco_get_state; softmax regression -- DOPT_SOFTMAX, dopt_load_shards_softmax,
  *      dopt_run_softmax, dopt_softmax_set_models, dopt_softmax_get_models; sparse (CSR) shards --
- *      dopt_load_shards_csr, dopt_run_sparse. */
+ *      dopt_load_shards_csr, dopt_run_sparse; local steps (periodic gossip) -- dopt_run_local,
+ *      DOPT_MAX_LOCAL_STEPS. */
 #define DOPT_ABI_VERSION 9
 
 typedef struct dopt_ctx dopt_ctx;
@@ -256,6 +257,29 @@ int dopt_run_dsgd_pipelined(dopt_ctx *ctx, int64_t t0, int64_t T, double eta0, i
 int dopt_run_gt(dopt_ctx *ctx, int64_t t0, int64_t T, double eta0, int64_t batch,
                 const int32_t *idx, double lam_grad, double lam_obj, double f_opt,
                 uint32_t flags, double *obj_out, double *cons_out, double *time_out);
+
+/* T communication rounds of D-SGD with local steps (Local SGD / periodic decentralized SGD), rounds
+ * t0..t0+T-1 -- the reference has no such trainer: every worker takes local_steps gradient steps on
+ * its shard between two gossip steps.  Round t, worker i, global step s = local_steps * t + k:
+ *   k = 0:                u = sum_j W_ij x_j - eta_s (grad f_i(x_i; B_{t,0}) + lam_grad x_i)
+ *   k = 1..local_steps-1: u = u - eta_s (grad f_i(u; B_{t,k}) + lam_grad u)
+ *   x_i <- u,             eta_s = eta0 / sqrt(s + 1)
+ * i.e. x_{s+1} = W_s x_s - eta_s g_s(x_s), W_s = W when s is a multiple of local_steps and I otherwise
+ * (the gradient is 0 for an empty shard); local_steps = 1 is the D-SGD round.  One fused launch per
+ * round on the device: the iterate stays in the workgroup across the steps and the neighbours' rows
+ * are read once.  T history rows (objective at the mean of the iterates after each round, consensus
+ * error) and T time stamps; flags and outputs as dopt_run_gt.  idx: [T * local_steps][N][batch] --
+ * one draw per worker per gradient step, in worker order, what dopt_mt_choice_rounds(T * local_steps,
+ * ..) returns -- or NULL, which needs full-shard batches.  A run split into several calls gives the
+ * bits of one call.  DOPT_ERR_INVALID: local_steps outside [1, DOPT_MAX_LOCAL_STEPS].
+ * DOPT_ERR_UNSUPPORTED: rows beyond the row-resident kernel (column-blocked contexts), mean mixing
+ * (dopt_set_mixing_mean; give the complete graph as CSR), a halo plan, the device sampler, softmax
+ * and sparse contexts. */
+#define DOPT_MAX_LOCAL_STEPS 64
+int dopt_run_local(dopt_ctx *ctx, int64_t t0, int64_t T, double eta0, int64_t batch,
+                   const int32_t *idx, double lam_grad, double lam_obj, double f_opt,
+                   uint32_t flags, int64_t local_steps, double *obj_out, double *cons_out,
+                   double *time_out);
 
 /* Softmax (multinomial logistic) regression over C classes -- the reference has no such
  * objective; it is the logistic path's round (trainer.py:161-193) with a matrix iterate W_i (C x d):
