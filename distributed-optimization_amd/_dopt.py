@@ -66,6 +66,9 @@ _SIGS = {
                                 ctypes.c_int),
     "dopt_run_gt": ([_P, _I64, _I64, _D, _I64, _P, _D, _D, _D, ctypes.c_uint32, _P, _P, _P], ctypes.c_int),
     "dopt_run_local": ([_P, _I64, _I64, _D, _I64, _P, _D, _D, _D, ctypes.c_uint32, _I64, _P, _P, _P], ctypes.c_int),
+    "dopt_run_pushsum": ([_P, _I64, _I64, _D, _I64, _P, _D, _D, _D, ctypes.c_uint32, _P, _P, _P], ctypes.c_int),
+    "dopt_pushsum_set_state": ([_P, _P], ctypes.c_int),
+    "dopt_pushsum_get_state": ([_P, _P, _P], ctypes.c_int),
     "dopt_gt_set_state": ([_P, _P, _P], ctypes.c_int),
     "dopt_gt_get_state": ([_P, _P, _P], ctypes.c_int),
     "dopt_run_choco": ([_P, _I64, _I64, _D, _I64, _P, _D, _D, _D, ctypes.c_uint32, _I64, _D, _P, _P, _P], ctypes.c_int),
@@ -537,6 +540,34 @@ class Engine:
         g = np.empty((self.n, self.d), dtype=np.float64)
         check(lib().dopt_gt_get_state(self._h, _ptr(y), _ptr(g)))
         return y, g
+
+    def run_pushsum(self, T, eta0, batch, lam_grad, lam_obj, f_opt=0.0, idx=None, t0=0,
+                    objective=True, consensus=True, want_time=True):
+        """dopt_run_pushsum: T rounds of push-sum SGD over the column-stochastic CSR matrix given to
+        set_topology (a directed graph), from the weights phi on the context; the iterates of
+        set_models / get_models are the numerators u.  Arguments and return value as run_gt."""
+        T = int(T)
+        obj = np.zeros(T) if objective else None
+        cons = np.zeros(T) if consensus else None
+        tim = np.zeros(T) if want_time else None
+        if idx is not None:
+            idx = np.ascontiguousarray(idx, dtype=np.int32)
+        flags = (RUN_OBJECTIVE if objective else 0) | (RUN_CONSENSUS if consensus else 0)
+        check(lib().dopt_run_pushsum(self._h, int(t0), T, float(eta0), int(batch), _ptr(idx), float(lam_grad),
+                                     float(lam_obj), float(f_opt), flags, _ptr(obj), _ptr(cons), _ptr(tim)))
+        return obj, cons, tim
+
+    def pushsum_set_state(self, phi=None):
+        """Push-sum weights phi (N); None = ones, a fresh chain."""
+        phi = None if phi is None else np.ascontiguousarray(phi, dtype=np.float64).reshape(self.n)
+        check(lib().dopt_pushsum_set_state(self._h, _ptr(phi)))
+
+    def pushsum_get_state(self):
+        """(phi, z): the weights (N) and the de-biased iterates u_i / phi_i (N x d)."""
+        phi = np.empty(self.n, dtype=np.float64)
+        z = np.empty((self.n, self.d), dtype=np.float64)
+        check(lib().dopt_pushsum_get_state(self._h, _ptr(phi), _ptr(z)))
+        return phi, z
 
     def run_choco(self, rounds, eta0, batch, lam_grad, lam_obj, f_opt=0.0, *, k, gamma, idx=None, t0=0,
                   objective=True, consensus=True, want_time=False):

@@ -275,6 +275,30 @@ hipError_t launch_local_f32(int problem, int cpl, bool met, const LocalArgs& a, 
 hipError_t launch_local_f64(int problem, int cpl, bool met, const LocalArgs& a, int n_workers, hipStream_t s);
 hipError_t launch_local_x32(int problem, int cpl, bool met, const LocalArgs& a, int n_workers, hipStream_t s);
 
+// ---- push-sum (k_round_pushsum.inc): directed graphs through a COLUMN-stochastic matrix, one launch
+// per round, one workgroup per worker
+//   v_i = sum_j A_ij u_j,   phi_i' = sum_j A_ij phi_j,   z_i = v_i / phi_i',
+//   u_i' = v_i - eta (grad f_i(z_i) + lam z_i),   zt_i = u_i' / phi_i'
+// r: the D-SGD round's arguments with the numerators u in x_old / x_new and the CSR matrix A by rows
+// (in-neighbours and the diagonal); r.xbar = zbar, the mean of the zt rows.  r.flags: F_STEP (without
+// it the launch only takes the metrics of zt at zbar), F_CONS, and -- full-shard batches only --
+// F_LOSS.  No halo rows, no F_MEAN.
+struct PushsumArgs {
+  RoundArgs r;
+  const void* phi_old;  // [n] T push-sum weights before the round (read only during the round)
+  void* phi_new;        // [n] T weights after the round
+  void* zt;             // [n x ld] T de-biased iterates: row i read (consensus of the state before the
+                        // round) and, with F_STEP, rewritten by workgroup i alone
+};
+// per element-type pair (pushsum_f32.hip / pushsum_f64.hip / pushsum_x32.hip); cpl = 16-byte DATA chunks per lane
+hipError_t launch_pushsum_f32(int problem, int cpl, bool met, const PushsumArgs& a, int n_workers, hipStream_t s);
+hipError_t launch_pushsum_f64(int problem, int cpl, bool met, const PushsumArgs& a, int n_workers, hipStream_t s);
+hipError_t launch_pushsum_x32(int problem, int cpl, bool met, const PushsumArgs& a, int n_workers, hipStream_t s);
+// zt[i] = u[i] / phi[i], i < n (T-typed, rows of ld elements): the de-biased iterates of a state no
+// round launch wrote; dtype 0 = float, 1 = double.
+hipError_t launch_pushsum_debias(int dtype, const void* u, const void* phi, void* zt, int64_t n, int64_t ld,
+                                 hipStream_t s);
+
 // ---- CHOCO-SGD (k_round_choco.inc): top-k compressed gossip with error feedback, one launch per
 // round, one workgroup per worker
 //   x_new_i = x_i - eta g_i + gamma (sum_j W_ij xhat_j - xhat_i),   xhat_i <- xhat_i + top_k(x_new_i - xhat_i)

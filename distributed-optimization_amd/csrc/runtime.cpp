@@ -152,6 +152,11 @@ struct dopt_ctx {
   // CHOCO-SGD (dopt_run_choco): ping-pong of the public copies, [N x ld] T, allocated (zero) on first use
   void* xh[2] = {nullptr, nullptr};
   int hcur = 0;
+  // push-sum (dopt_run_pushsum): the weights phi, [2][N] T with the current ones in half pcur, and the
+  // de-biased iterates zt = u / phi, [N x ld] T; allocated (phi = 1) on first use
+  void* ps_phi = nullptr;
+  int pcur = 0;
+  void* ps_zt = nullptr;
   // softmax regression (dopt_load_shards_softmax): classes of the context, 0 for the vector objectives.  The
   // state rows (xs, xbar, part, S) then hold sm_C blocks of ld elements, class-major; ld / nch stay the data row's
   int sm_C = 0;
@@ -514,6 +519,9 @@ int alloc_state(dopt_ctx* c) {
   dfree(c->xh[0]);  // ... and so are the public copies of dopt_run_choco
   dfree(c->xh[1]);
   c->hcur = 0;
+  dfree(c->ps_phi);  // ... and the push-sum weights of dopt_run_pushsum (ones again on first use)
+  dfree(c->ps_zt);
+  c->pcur = 0;
   c->cur = 0;
   c->gcur = 0;
   c->xb = 0;
@@ -1414,7 +1422,7 @@ int dopt_destroy(dopt_ctx* c) {
   if (c->stream) (void)hipStreamSynchronize(c->stream);
   if (c->own_stream) (void)hipStreamSynchronize(c->own_stream);
   for (void** p : {&c->X, &c->y, &c->Xo, &c->yo, &c->xs[0], &c->xs[1], &c->xg[0], &c->xg[1], &c->G, &c->ys[0], &c->ys[1],
-                   &c->gprev, &c->xh[0], &c->xh[1], &c->xbar[0], &c->xbar[1], &c->cw, &c->staging, &c->sx, &c->wdiag, &c->coef})
+                   &c->gprev, &c->xh[0], &c->xh[1], &c->ps_phi, &c->ps_zt, &c->xbar[0], &c->xbar[1], &c->cw, &c->staging, &c->sx, &c->wdiag, &c->coef})
     dfree(*p);
   dfree_t(c->off);
   dfree_t(c->offo);
@@ -2242,6 +2250,189 @@ int dopt_run_local(dopt_ctx* c, int64_t t0, int64_t T, double eta0, int64_t batc
   if (c && (c->sm_C || c->sparse)) return no_dense(c, __func__);
   return run_local(c, t0, T, eta0, batch, idx, lam_grad, lam_obj, f_opt, flags, local_steps, obj_out, cons_out,
                    time_out);
+}
+
+// ---------------------------------------------------------------------------- push-sum
+namespace {
+
+// The current weights (half pcur of ps_phi) from N host doubles, or -- phi == NULL -- all ones.
+int upload_phi(dopt_ctx* c, const double* phi) {
+  std::vector<char> tmp((size_t)std::max<int64_t>(1, c->n) * c->esz);
+  for (int64_t i = 0; i < c->n; ++i) {
+    const double v = phi ? phi[i] : 1.0;
+    if (c->dtype == DOPT_F32) ((float*)tmp.data())[i] = (float)v;
+    else ((double*)tmp.data())[i] = v;
+  }
+  HIPOK(hipMemcpyAsync((char*)c->ps_phi + (size_t)c->pcur * c->n * c->esz, tmp.data(), (size_t)c->n * c->esz,
+                       hipMemcpyHostToDevice, c->stream));
+  HIPOK(hipStreamSynchronize(c->stream));
+  return DOPT_OK;
+}
+
+// State of dopt_run_pushsum: phi = 1 until a run or dopt_pushsum_set_state says otherwise.
+int ensure_pushsum(dopt_ctx* c) {
+  if (c->ps_phi && c->ps_zt) return DOPT_OK;
+  const int64_t n1 = std::max<int64_t>(1, c->n);
+  int rc;
+  if ((rc = dalloc(&c->ps_phi, (size_t)(2 * n1) * c->esz))) return rc;
+  if ((rc = dalloc(&c->ps_zt, (size_t)n1 * c->ld * c->esz))) return rc;
+  c->pcur = 0;
+  return upload_phi(c, nullptr);
+}
+
+void* phi_half(dopt_ctx* c, int half) { return (char*)c->ps_phi + (size_t)half * c->n * c->esz; }
+
+hipError_t launch_pushsum(dopt_ctx* c, bool met, const PushsumArgs& g) {
+  if (c->dtype == DOPT_F32) return launch_pushsum_f32(c->problem, c->cpl, met, g, (int)c->n, c->stream);
+  if (c->xdtype == DOPT_F32) return launch_pushsum_x32(c->problem, c->cpl, met, g, (int)c->n, c->stream);
+  return launch_pushsum_f64(c->problem, c->cpl, met, g, (int)c->n, c->stream);
+}
+
+int check_pushsum(dopt_ctx* c) {
+  if (!c->have_data) return fail(DOPT_ERR_STATE, "no shards loaded");
+  if (c->split)
+    return fail(DOPT_ERR_UNSUPPORTED, "push-sum: rows of %lld elements are column-blocked; the push-sum round holds "
+                "a row per wave (at most %d 16-byte chunks per lane)", (long long)c->d,
+                max_chunks_per_lane(c->dtype, c->xdtype));
+  return DOPT_OK;
+}
+
+// zt = u / phi of the current state, for a state the round kernel did not write.
+int debias_current(dopt_ctx* c) {
+  HIPOK(launch_pushsum_debias(c->dtype == DOPT_F32 ? 0 : 1, c->xs[c->cur], phi_half(c, c->pcur), c->ps_zt, c->n, c->ld,
+                              c->stream));
+  return DOPT_OK;
+}
+
+// T rounds of push-sum SGD on run_gt's schedule: k_round_pushsum, then the column sums of the
+// de-biased iterates zt the launch stored (xbar = zbar) with the history row of the previous round
+// folded in.  Round h's launch takes the metrics of zt_h at zbar_h (history[h - 1]) in its pass; the
+// row of the last state takes one more launch of the same kernel without the step.  A call starts by
+// forming zt = u / phi with the division the kernel's epilogue uses, so a run split into several
+// calls computes every history entry with the same code on the same bits.  Host minibatches (idx)
+// and a separate objective dataset: the kernel fuses the consensus only and the objective takes the
+// metrics-only pass at zbar after every round.
+int run_pushsum(dopt_ctx* c, int64_t t0, int64_t T, double eta0, int64_t batch, const int32_t* idx, double lam_grad,
+                double lam_obj, double f_opt, uint32_t flags, double* obj_out, double* cons_out, double* time_out) {
+  CHECK_ARG(c, "ctx is NULL");
+  int rc;
+  if ((rc = check_pushsum(c))) return rc;
+  if (!c->have_topo) return fail(DOPT_ERR_STATE, "no topology set");
+  if (c->mean_mix)
+    return fail(DOPT_ERR_UNSUPPORTED, "push-sum: mean mixing (dopt_set_mixing_mean) is not supported; give the "
+                "column-stochastic matrix as CSR (dopt_set_topology)");
+  if (c->n_halo > 0 || c->n_send > 0 || c->sptr)
+    return fail(DOPT_ERR_UNSUPPORTED, "push-sum: contexts with a halo plan (multi-GPU slices) are not supported");
+  if (!idx && batch < c->max_m && c->sampler == DOPT_SAMPLE_DEVICE)
+    return fail(DOPT_ERR_UNSUPPORTED, "push-sum: the device sampler is not supported; pass idx");
+  if ((rc = check_run(c, T, batch, idx, true))) return rc;
+  if ((rc = set_device(c))) return rc;
+  if ((rc = rs_end(c))) return rc;
+  c->carry_pending = false;
+  c->send_fresh = false;
+  if (T == 0) return DOPT_OK;
+  if ((rc = ensure_hist(c, T + 1))) return rc;
+  if ((rc = ensure_pushsum(c))) return rc;
+  const bool want_obj = flags & DOPT_RUN_OBJECTIVE, want_cons = flags & DOPT_RUN_CONSENSUS;
+  const bool metrics = want_obj || want_cons;
+  const bool fuse_loss = want_obj && !idx && !c->obj_sep;  // the pass walks every objective row
+  const bool pass_loss = want_obj && !fuse_loss;
+  const int64_t CH = idx ? idx_chunk_rounds(c, T, batch) : 1;
+  int& xb = c->xb;
+  // zt and zbar of the starting state; the spare xbar takes every later zbar
+  auto colsum_zt = [&](void* out, uint64_t* stamp, const FoldArgs* fold) {
+    return launch_colsum(c->dtype, c->ps_zt, c->n, c->ld, (int32_t)c->nchs, kRowsPerGroup, c->part, stamp, n_div(c), out,
+                         nullptr, 0.0, 0, c->stream, c->S, fold);
+  };
+  if ((rc = debias_current(c))) return rc;
+  HIPOK(colsum_zt(c->xbar[xb], nullptr, nullptr));
+  HIPOK(launch_stamp(c->stamps, c->stream));
+
+  auto ps_args = [&](bool step, bool met) {
+    PushsumArgs g;
+    memset(&g, 0, sizeof(g));
+    g.r = base_args(c);
+    g.r.x_old = c->xs[c->cur];
+    g.r.x_new = c->xs[c->cur ^ 1];
+    g.r.xbar = c->xbar[xb];
+    g.r.lam = lam_grad;
+    g.r.b = batch;
+    g.r.flags |= (step ? F_STEP : 0) | (met && want_cons ? F_CONS : 0) | (met && fuse_loss ? F_LOSS : 0);
+    g.phi_old = phi_half(c, c->pcur);
+    g.phi_new = phi_half(c, c->pcur ^ 1);
+    g.zt = c->ps_zt;
+    if (g.r.flags & F_LOSS) c->loss_groups = c->n;  // per-worker loss slabs
+    return g;
+  };
+  // history row `row` = the slabs of the current launch (and, pass_loss, of the last metrics pass) at xbar[xb]
+  auto fold_args = [&](int64_t row) {
+    double* hr = c->hraw + 3 * row;
+    return FoldArgs{want_cons ? c->slab_cons : nullptr, c->n, want_obj ? c->slab_loss : nullptr, c->loss_groups,
+                    want_obj ? c->xbar[xb] : nullptr, hr, hr + 1, hr + 2};
+  };
+
+  for (int64_t h = 0; h < T; ++h) {
+    const int64_t t = t0 + h;
+    if (idx && h % CH == 0) {
+      if ((rc = upload_idx_chunk(c, idx, h, std::min(CH, T - h), batch))) return rc;
+    }
+    const bool met = metrics && h > 0;
+    PushsumArgs g = ps_args(true, met);
+    g.r.idx = idx ? c->idx + (h % CH) * c->n * batch : nullptr;
+    g.r.eta = eta0 / sqrt((double)(t + 1));
+    if (c->prof && (rc = prof_event(c, false))) return rc;
+    HIPOK(launch_pushsum(c, metrics, g));
+    if (c->prof && (rc = prof_event(c, true))) return rc;
+    // zbar of the round's de-biased iterates and the stamp of the round's end; history[h - 1] rides the launch
+    const FoldArgs fold = fold_args(met ? h - 1 : 0);
+    HIPOK(colsum_zt(c->xbar[xb ^ 1], c->stamps + h + 1, met ? &fold : nullptr));
+    if (pass_loss && (rc = metrics_pass(c, c->ps_zt, c->xbar[xb ^ 1], false, false, true))) return rc;
+    c->cur ^= 1;
+    c->pcur ^= 1;
+    xb ^= 1;
+  }
+  if (metrics) {  // the row of the last state; the column sums land in the spare xbar
+    const PushsumArgs g = ps_args(false, true);
+    if (want_cons || fuse_loss) HIPOK(launch_pushsum(c, true, g));
+    const FoldArgs fold = fold_args(T - 1);
+    HIPOK(colsum_zt(c->xbar[xb ^ 1], nullptr, &fold));
+  }
+  return finish_run(c, T, T, lam_obj, f_opt, want_obj ? obj_out : nullptr, want_cons ? cons_out : nullptr,
+                    time_out);
+}
+
+}  // namespace
+
+int dopt_run_pushsum(dopt_ctx* c, int64_t t0, int64_t T, double eta0, int64_t batch, const int32_t* idx,
+                     double lam_grad, double lam_obj, double f_opt, uint32_t flags, double* obj_out, double* cons_out,
+                     double* time_out) {
+  if (c && (c->sm_C || c->sparse)) return no_dense(c, __func__);
+  return run_pushsum(c, t0, T, eta0, batch, idx, lam_grad, lam_obj, f_opt, flags, obj_out, cons_out, time_out);
+}
+
+int dopt_pushsum_set_state(dopt_ctx* c, const double* phi) {
+  if (c && (c->sm_C || c->sparse)) return no_dense(c, __func__);
+  CHECK_ARG(c, "ctx is NULL");
+  int rc;
+  if ((rc = check_pushsum(c))) return rc;
+  if ((rc = set_device(c))) return rc;
+  if ((rc = ensure_pushsum(c))) return rc;
+  return upload_phi(c, phi);
+}
+
+int dopt_pushsum_get_state(dopt_ctx* c, double* phi, double* z) {
+  if (c && (c->sm_C || c->sparse)) return no_dense(c, __func__);
+  CHECK_ARG(c, "ctx is NULL");
+  int rc;
+  if ((rc = check_pushsum(c))) return rc;
+  if ((rc = set_device(c))) return rc;
+  if ((rc = ensure_pushsum(c))) return rc;
+  if (phi && (rc = download_rows(c, c->dtype, phi_half(c, c->pcur), phi, 1, c->n, c->n))) return rc;
+  if (z) {
+    if ((rc = debias_current(c))) return rc;
+    if ((rc = download_rows(c, c->dtype, c->ps_zt, z, c->n, c->d, c->ld))) return rc;
+  }
+  return DOPT_OK;
 }
 
 // ---------------------------------------------------------------------------- CHOCO-SGD

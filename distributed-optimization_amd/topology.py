@@ -18,6 +18,14 @@ Topologies:
   fully_connected   trainer.py:109-110
   random_regular    not in the reference: the random k-regular graph of
                     BASELINE.json config C3 (pairing model, fixed seed)
+
+Directed topologies (not in the reference; push-sum, trainer algorithm='push_sum'): a
+DirectedTopology is built from sorted OUT-neighbour lists and carries the COLUMN-stochastic
+matrix A_ij = 1 / (1 + outdeg_j) on the edges j -> i and on the diagonal, in CSR by rows.
+  directed_ring     i -> i+1
+  exponential       i -> (i + 2^k) mod n for every 2^k < n
+  random_digraph    the directed ring plus k - 1 further distinct random out-neighbours per
+                    node (fixed seed): unbalanced in-degrees
 """
 from __future__ import annotations
 
@@ -167,6 +175,90 @@ def random_regular(n, k, seed=0, max_tries=10000):
     raise RuntimeError("random_regular: no simple graph found")
 
 
+class DirectedTopology:
+    """Out-neighbour lists + push-sum weights.  `row_ptr`, `col`, `w`: row i holds the
+    in-neighbours of i plus i, ascending, with A_ij = 1 / (1 + outdeg_j) (one IEEE division),
+    so every COLUMN of A sums to 1."""
+
+    directed = True
+
+    def __init__(self, name, out_neighbours):
+        self.name = name
+        self.n = n = len(out_neighbours)
+        self.out_neighbours = [np.asarray(nb, dtype=np.int64) for nb in out_neighbours]
+        self.out_degrees = np.array([float(len(nb)) for nb in self.out_neighbours], dtype=np.float64)
+        self.degrees = self.out_degrees
+        src = np.concatenate([np.full(len(nb), j, dtype=np.int64) for j, nb in enumerate(self.out_neighbours)] +
+                             [np.arange(n, dtype=np.int64)])
+        dst = np.concatenate(self.out_neighbours + [np.arange(n, dtype=np.int64)])
+        if len(np.unique(dst * max(n, 1) + src)) != len(src):
+            raise ValueError(f"out-neighbour lists with a self loop or a repeated edge (Topology: {name})")
+        order = np.lexsort((src, dst))  # by row, columns ascending
+        self.col = src[order].astype(np.int32)
+        self.w = 1.0 / (1.0 + self.out_degrees[src[order]])
+        self.row_ptr = np.zeros(n + 1, dtype=np.int64)
+        np.cumsum(np.bincount(dst, minlength=n), out=self.row_ptr[1:])
+
+    nnz = Topology.nnz
+    dense_W = Topology.dense_W
+    sparse_W = Topology.sparse_W
+
+    @classmethod
+    def from_undirected(cls, topo):
+        """The directed form of an undirected Topology: the same neighbour lists read as
+        out-neighbours (every edge both ways), out-degree weights."""
+        return cls(topo.name, [np.asarray(nb, dtype=np.int64)[np.asarray(nb, dtype=np.int64) != i]
+                               for i, nb in enumerate(topo.neighbours)])
+
+    def dense_adjacency(self):
+        """adj[j, i] = 1 for every edge j -> i."""
+        adj = np.zeros((self.n, self.n))
+        for j, nb in enumerate(self.out_neighbours):
+            adj[j, nb] = 1.0
+        return adj
+
+    def check(self):
+        """Columns of A sum to 1 and the graph is strongly connected."""
+        if self.n == 0:
+            return
+        cs = np.bincount(self.col, weights=self.w, minlength=self.n)
+        assert np.allclose(cs, 1.0), f"Columns of A do not sum to 1 (Topology: {self.name})"
+        from scipy.sparse.csgraph import connected_components
+
+        nc, _ = connected_components(self.sparse_W(), directed=True, connection="strong")
+        assert nc == 1, f"The graph is not strongly connected (Topology: {self.name})"
+
+
+def directed_ring(n):
+    return DirectedTopology("directed_ring", [[(i + 1) % n] if n > 1 else [] for i in range(n)])
+
+
+def exponential(n):
+    hops = [1 << k for k in range(max(n, 1).bit_length()) if (1 << k) < n]
+    return DirectedTopology("exponential", [sorted({(i + h) % n for h in hops}) for i in range(n)])
+
+
+def random_digraph(n, k, seed=0):
+    """The directed ring plus k - 1 further distinct random out-neighbours per node (no self
+    loops): out-degree k everywhere, in-degrees unbalanced, so the push-sum weights leave 1."""
+    if n > 1 and not 1 <= k <= n - 1:
+        raise ValueError(f"no simple digraph of out-degree {k} on {n} vertices")
+    rng = np.random.default_rng(seed)
+    nbrs = []
+    for i in range(n):
+        if n == 1:
+            nbrs.append([])
+            continue
+        ring_nb = (i + 1) % n
+        others = np.delete(np.arange(n, dtype=np.int64), [i, ring_nb])
+        extra = rng.choice(others, size=k - 1, replace=False) if k > 1 else np.zeros(0, np.int64)
+        nbrs.append(sorted([ring_nb] + extra.tolist()))
+    return DirectedTopology("random_digraph", nbrs)
+
+
+DIRECTED = ("directed_ring", "exponential", "random_digraph")
+
+
 def relabel(topo, order):
     """The same graph with new vertex ids: new id k is old vertex order[k] (a permutation).
     MH weights are recomputed on the new ids (per edge the same value; W_ii can differ in
@@ -189,4 +281,10 @@ def build(name, n, config=None):
         return fully_connected(n)
     if name == "random_regular":
         return random_regular(n, int(config.get("regular_degree", 4)), int(config.get("topology_seed", 0)))
+    if name == "directed_ring":
+        return directed_ring(n)
+    if name == "exponential":
+        return exponential(n)
+    if name == "random_digraph":
+        return random_digraph(n, int(config.get("regular_degree", 4)), int(config.get("topology_seed", 0)))
     raise ValueError(f"Wrong topology: {name}")

@@ -32,7 +32,20 @@ Config keys beyond the reference's (all optional):
              'choco' (CHOCO-SGD, top-k compressed gossip with error feedback: the workers
              mix through public copies xhat_i, x_i <- x_i - eta_t g_i + choco_gamma
              (sum_j W_ij xhat_j - xhat_i), and send only the compression_k largest entries of
-             x_i - xhat_i, which the receivers add to xhat_i; same restrictions)
+             x_i - xhat_i, which the receivers add to xhat_i; same restrictions) or
+             'push_sum' (push-sum SGD / stochastic gradient push, for DIRECTED graphs: the workers
+             mix numerators u_i and scalar weights phi_i through the column-stochastic matrix
+             A_ij = 1 / (1 + outdeg_j) and take the gradient at the de-biased z_i = u_i / phi_i,
+             v_i = sum_j A_ij u_j, phi_i <- sum_j A_ij phi_j, z_i = v_i / phi_i,
+             u_i <- v_i - eta_t g_i(z_i); one fused launch per round.  Topologies: 'directed_ring',
+             'exponential', 'random_digraph' (regular_degree = out-degree, topology_seed) -- these
+             three with push_sum only, ValueError otherwise -- or an undirected name, run in its
+             directed form (every edge both ways, out-degree weights).  For a directed name W is
+             the dense A and degrees the out-degrees.  After run, Worker.x = z_i, the returned
+             model is mean_i z_i, and total_floats_transmitted grows per round by
+             sum(out_degrees) * (n_features + 1): u and phi travel on every directed edge.  Single
+             process, host sampling, local_steps = 1, dense 'logistic' / 'quadratic' workers, no
+             checkpoints)
   compression_k  algorithm='choco', required: entries sent per worker and round, an int in
              [1, n_features]
   choco_gamma    algorithm='choco', required: the consensus step size, a float in (0, 1]
@@ -717,10 +730,22 @@ class DecentralizedTrainer:
 
     def _create_mixing_matrix(self):
         """Metropolis-Hastings mixing matrix (trainer.py:91-136), built sparse."""
+        algorithm = self.config.get("algorithm", "dsgd")
+        directed = self.topology in _topology.DIRECTED
+        if directed and algorithm != "push_sum":
+            raise ValueError(f"topology {self.topology!r} is directed: it runs algorithm='push_sum', not {algorithm!r}")
         topo = _topology.build(self.topology, self.n_workers, self.config)
         self._topo = topo
         self.degrees = topo.degrees
         dense = self.n_workers <= DENSE_LIMIT
+        if directed:  # W = the column-stochastic A; no symmetric check, no spectral gap
+            self._directed = topo
+            self.adj = topo.dense_adjacency() if dense else None
+            if self.n_workers > 0:
+                topo.check()
+            return topo.dense_W() if dense else topo.sparse_W()
+        if algorithm == "push_sum":  # an undirected graph runs in its directed form
+            self._directed = _topology.DirectedTopology.from_undirected(topo)
         self.adj = topo.dense_adjacency() if dense else None
         W = topo.dense_W() if dense else topo.sparse_W()
         if self.n_workers > 0:
@@ -760,6 +785,8 @@ class DecentralizedTrainer:
         algorithm = cfg.get("algorithm", "dsgd")
         if algorithm == "choco":
             return self._run_choco(int(n_iterations), X_full, y_full, f_opt, lam_grad, reg_param, start_time)
+        if algorithm == "push_sum":
+            return self._run_push_sum(int(n_iterations), X_full, y_full, f_opt, lam_grad, reg_param, start_time)
         if algorithm != "dsgd":
             return self._run_gradient_tracking(algorithm, int(n_iterations), X_full, y_full, f_opt, lam_grad,
                                                reg_param, start_time)
@@ -821,7 +848,8 @@ class DecentralizedTrainer:
         from y = g = 0.  Every unsupported combination is refused before any device call."""
         cfg = self.config
         if algorithm != "gradient_tracking":
-            raise ValueError(f"unknown algorithm {algorithm!r}: 'dsgd', 'gradient_tracking' or 'choco'")
+            raise ValueError(f"unknown algorithm {algorithm!r}: 'dsgd', 'gradient_tracking' or 'choco' -- or 'push_sum', "
+                             "the one that runs directed graphs")
         if _dist_info(cfg) is not None:
             raise NotImplementedError("gradient tracking runs in a single process (no multi-rank job)")
         if self._mean_mixing() and self._topo.uniform_offdiag() is not None:
@@ -976,6 +1004,47 @@ class DecentralizedTrainer:
         print(f"Decentralized ({self.topology}) training finished. Time: {time.time() - start_time:.2f}s")
         final_avg_model = np.mean([worker.x for worker in self.workers], axis=0)
         return self.history, final_avg_model
+
+    def _run_push_sum(self, T, X_full, y_full, f_opt, lam_grad, reg_param, start_time):
+        """config 'algorithm' = 'push_sum': the rounds of Engine.run_pushsum in D-SGD's chunk loop over the
+        column-stochastic matrix of the directed graph, from u_i = Worker.x and phi = 1.  A worker sends
+        u_i and phi_i along each of its out-edges, so total_floats_transmitted grows per round by
+        sum(out_degrees) * (n_features + 1).  Every unsupported combination is refused before any device
+        call (local_steps, softmax and sparse workers: by their own runners)."""
+        cfg = self.config
+        if _dist_info(cfg) is not None:
+            raise NotImplementedError("push-sum runs in a single process (no multi-rank job)")
+        ck_keys = [k for k in ("checkpoint_path", "checkpoint_every", "resume_from") if cfg.get(k)]
+        if ck_keys:
+            raise NotImplementedError(f"push-sum does not checkpoint (config {ck_keys})")
+        if cfg.get("sampling", "legacy") == "device":
+            raise NotImplementedError("push-sum draws its minibatches on the host (sampling='legacy')")
+        eng = _engine(self.workers, self.n_features, cfg, X_full=X_full, y_full=y_full)
+        want_obj = _set_objective_data(eng, self.workers, self.n_features, X_full, y_full, _sampled_key(cfg))
+        t = self._directed
+        eng.set_topology(t.row_ptr, t.col, t.w)
+        eng.set_models(np.stack([np.asarray(w.x, dtype=np.float64) for w in self.workers]))
+        eng.pushsum_set_state(None)
+        iteration_transmission = int(np.sum(t.out_degrees)) * (self.n_features + 1)
+        eta0 = cfg["learning_rate_eta0"]
+        loop_start = time.perf_counter()
+        with closing(_index_chunks(self.workers, T, cfg)) as chunks:
+            for t0, n, b, idx, _ in chunks:
+                t_host = time.time() - start_time
+                obj, cons, tim = eng.run_pushsum(n, eta0, b, lam_grad, reg_param, f_opt, idx=idx, t0=t0,
+                                                 objective=want_obj, consensus=True, want_time=True)
+                self.history["consensus_error"].extend(list(cons))
+                if want_obj:
+                    self.history["objective"].extend(list(obj))
+                self.history["time"].extend((tim + t_host).tolist())
+                self.total_floats_transmitted += n * iteration_transmission
+        self.loop_seconds = time.perf_counter() - loop_start
+        _, z = eng.pushsum_get_state()
+        for i, worker in enumerate(self.workers):
+            worker.x = z[i, :]
+        _warn_nonfinite(self.history, self.config)
+        print(f"Decentralized ({self.topology}) training finished. Time: {time.time() - start_time:.2f}s")
+        return self.history, np.mean(z, axis=0)
 
     def _run_softmax(self, T, X_full, y_full, f_opt, start_time):
         """config 'problem_type' = 'softmax' with 'num_classes' = C: the rounds of Engine.run_softmax

@@ -61,7 +61,8 @@ extern "C" {
  *      dopt_choco_get_state; softmax regression -- DOPT_SOFTMAX, dopt_load_shards_softmax,
  *      dopt_run_softmax, dopt_softmax_set_models, dopt_softmax_get_models; sparse (CSR) shards --
  *      dopt_load_shards_csr, dopt_run_sparse; local steps (periodic gossip) -- dopt_run_local,
- *      DOPT_MAX_LOCAL_STEPS. */
+ *      DOPT_MAX_LOCAL_STEPS; push-sum (directed graphs) -- dopt_run_pushsum, dopt_pushsum_set_state,
+ *      dopt_pushsum_get_state. */
 #define DOPT_ABI_VERSION 9
 
 typedef struct dopt_ctx dopt_ctx;
@@ -280,6 +281,40 @@ int dopt_run_local(dopt_ctx *ctx, int64_t t0, int64_t T, double eta0, int64_t ba
                    const int32_t *idx, double lam_grad, double lam_obj, double f_opt,
                    uint32_t flags, int64_t local_steps, double *obj_out, double *cons_out,
                    double *time_out);
+
+/* T rounds of push-sum SGD (subgradient-push, Nedic & Olshevsky; stochastic gradient push, Assran et
+ * al.), rounds t0..t0+T-1 -- the reference has no such trainer: decentralized SGD over a DIRECTED
+ * graph.  The matrix A given to dopt_set_topology is then COLUMN-stochastic with a positive diagonal
+ * (A_ij = 1 / (1 + outdeg_j) on the edges j -> i and on the diagonal, which every sender can form
+ * from its own out-degree), in CSR by rows: row i lists the in-neighbours j of i and i itself, columns
+ * ascending.  Column-stochasticity is the caller's contract; the engine does not check it.  State per
+ * worker: the numerator u_i -- it lives in the context's iterates, so dopt_set_models /
+ * dopt_get_models read and write u --, the push-sum weight phi_i > 0 (1 at the start of a chain) and
+ * the de-biased iterate z_i = u_i / phi_i.  Round t, worker i:
+ *   v_i    = sum_j A_ij u_j                          (CSR order)
+ *   phi_i' = sum_j A_ij phi_j                        (CSR order)
+ *   z_i    = v_i / phi_i'                            (element-wise division)
+ *   g_i    = grad f_i(z_i; B_{t,i}) + lam_grad z_i   (0 for an empty shard)
+ *   u_i'   = v_i - eta_t g_i,   eta_t = eta0 / sqrt(t + 1)
+ * History row t is taken at the de-biased iterates after the round, zt_i = u_i' / phi_i':
+ *   objective = f(mean_i zt_i; all data) + (lam_obj / 2) ||.||^2 - f_opt,
+ *   consensus = mean_i ||zt_i - mean_k zt_k||^2.
+ * With a doubly stochastic A and phi = 1 this is u' = W u - eta g(W u): combine-then-adapt, not the
+ * round of dopt_run_dsgd, which takes the gradient at the worker's own iterate.  sum_i phi_i = N in
+ * every round.  One fused launch per round; arguments, flags, outputs and history as dopt_run_gt.  A
+ * run split into several calls gives the bits of one call.  Loading or generating shards resets phi
+ * to ones; dopt_set_models leaves phi alone.  DOPT_ERR_UNSUPPORTED: rows beyond the row-resident
+ * kernel (column-blocked contexts), mean mixing (dopt_set_mixing_mean), a halo plan, the device
+ * sampler, softmax and sparse contexts. */
+int dopt_run_pushsum(dopt_ctx *ctx, int64_t t0, int64_t T, double eta0, int64_t batch,
+                     const int32_t *idx, double lam_grad, double lam_obj, double f_opt,
+                     uint32_t flags, double *obj_out, double *cons_out, double *time_out);
+
+/* Push-sum state of dopt_run_pushsum at the boundary: phi = the N weights (float64; NULL in
+ * dopt_pushsum_set_state: all ones, a fresh chain), z = the de-biased iterates u_i / phi_i, N x d
+ * row-major float64.  A NULL argument of dopt_pushsum_get_state is skipped. */
+int dopt_pushsum_set_state(dopt_ctx *ctx, const double *phi);
+int dopt_pushsum_get_state(dopt_ctx *ctx, double *phi, double *z);
 
 /* Softmax (multinomial logistic) regression over C classes -- the reference has no such
  * objective; it is the logistic path's round (trainer.py:161-193) with a matrix iterate W_i (C x d):
