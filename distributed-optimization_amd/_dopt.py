@@ -24,6 +24,7 @@ OK, ERR_INVALID, ERR_HIP, ERR_STATE, ERR_UNSUPPORTED, ERR_COMM, ERR_NOMEM, ERR_R
 LOGISTIC, QUADRATIC, SOFTMAX = 0, 1, 2
 F32, F64 = 0, 1
 RUN_OBJECTIVE, RUN_CONSENSUS = 1, 2
+RUN_CONST_STEP = 4  # run_gt_saga only
 SAMPLE_HOST, SAMPLE_DEVICE = 0, 1
 MAX_BIP_ROWS = 65536  # dopt.h DOPT_MAX_BIP_ROWS: minibatch gradient inside the metrics pass
 PROBLEMS = {"logistic": LOGISTIC, "quadratic": QUADRATIC, "softmax": SOFTMAX}
@@ -69,6 +70,9 @@ _SIGS = {
     "dopt_run_pushsum": ([_P, _I64, _I64, _D, _I64, _P, _D, _D, _D, ctypes.c_uint32, _P, _P, _P], ctypes.c_int),
     "dopt_pushsum_set_state": ([_P, _P], ctypes.c_int),
     "dopt_pushsum_get_state": ([_P, _P, _P], ctypes.c_int),
+    "dopt_run_gt_saga": ([_P, _I64, _I64, _D, _I64, _P, _D, _D, _D, ctypes.c_uint32, _P, _P, _P], ctypes.c_int),
+    "dopt_saga_get_state": ([_P, _P, _P], ctypes.c_int),
+    "dopt_saga_reset": ([_P], ctypes.c_int),
     "dopt_gt_set_state": ([_P, _P, _P], ctypes.c_int),
     "dopt_gt_get_state": ([_P, _P, _P], ctypes.c_int),
     "dopt_run_choco": ([_P, _I64, _I64, _D, _I64, _P, _D, _D, _D, ctypes.c_uint32, _I64, _D, _P, _P, _P], ctypes.c_int),
@@ -540,6 +544,36 @@ class Engine:
         g = np.empty((self.n, self.d), dtype=np.float64)
         check(lib().dopt_gt_get_state(self._h, _ptr(y), _ptr(g)))
         return y, g
+
+    def run_gt_saga(self, T, eta0, batch, lam_grad, lam_obj, f_opt=0.0, idx=None, t0=0,
+                    objective=True, consensus=True, want_time=True, const_step=False):
+        """dopt_run_gt_saga: T rounds of GT-SAGA (gradient tracking along the SAGA estimate) from the
+        tracker and table state on the context; a chain's first call opens with the pass over every
+        row.  idx rows must be distinct within a worker and a round (mt_choice_rounds draws them so).
+        const_step: eta_t = eta0 instead of eta0 / sqrt(t + 1).  Arguments and return value as run_gt."""
+        T = int(T)
+        obj = np.zeros(T) if objective else None
+        cons = np.zeros(T) if consensus else None
+        tim = np.zeros(T) if want_time else None
+        if idx is not None:
+            idx = np.ascontiguousarray(idx, dtype=np.int32)
+        flags = ((RUN_OBJECTIVE if objective else 0) | (RUN_CONSENSUS if consensus else 0)
+                 | (RUN_CONST_STEP if const_step else 0))
+        check(lib().dopt_run_gt_saga(self._h, int(t0), T, float(eta0), int(batch), _ptr(idx), float(lam_grad),
+                                     float(lam_obj), float(f_opt), flags, _ptr(obj), _ptr(cons), _ptr(tim)))
+        return obj, cons, tim
+
+    def saga_get_state(self):
+        """(tab, gbar): the SAGA table (one coefficient per shard row, shard order) and the mean table
+        gradients (N x d)."""
+        tab = np.empty(int(np.sum(self.shard_rows)), dtype=np.float64)
+        gbar = np.empty((self.n, self.d), dtype=np.float64)
+        check(lib().dopt_saga_get_state(self._h, _ptr(tab), _ptr(gbar)))
+        return tab, gbar
+
+    def saga_reset(self):
+        """The next run_gt_saga opens a new chain (table pass); trackers y and g are zeroed."""
+        check(lib().dopt_saga_reset(self._h))
 
     def run_pushsum(self, T, eta0, batch, lam_grad, lam_obj, f_opt=0.0, idx=None, t0=0,
                     objective=True, consensus=True, want_time=True):

@@ -256,6 +256,28 @@ hipError_t launch_gt_f32(int problem, int cpl, bool met, const GtArgs& a, int n_
 hipError_t launch_gt_f64(int problem, int cpl, bool met, const GtArgs& a, int n_workers, hipStream_t s);
 hipError_t launch_gt_x32(int problem, int cpl, bool met, const GtArgs& a, int n_workers, hipStream_t s);
 
+// ---- GT-SAGA (k_round_saga.inc): gradient tracking along the SAGA estimate, one launch per round,
+// one workgroup per worker
+//   s = sum_{j in B} (coef_j - tab[j]) row_j,   g_new_i = s / nb + gbar_i + lam x_i,
+//   gbar_i += s / m_i,   tab[j] = coef_j (j in B),   then k_round_gt's y_new_i, x_new_i and g_i <- g_new_i
+// r, y_old, y_new, g_prev: as GtArgs.  init != 0: the chain's opening pass instead -- every shard row
+// at x_old with c_old = 0, tab[j] = coef_j, gbar_i = s / m_i; r.idx and r.flags are ignored, no
+// metrics.  A launch without F_STEP (and init = 0) takes metrics only and leaves tab / gbar alone.
+struct SagaArgs {
+  RoundArgs r;
+  const void* y_old;  // [n x ld] T trackers before the round (read only during the round)
+  void* y_new;        // [n x ld] T trackers after the round
+  void* g_prev;       // [n x ld] T the previous gradient estimates, replaced in place
+  void* tab;          // [rows] T the SAGA table, one coefficient per shard row; only workgroup i touches
+                      // rows off[i] .. off[i + 1), and r.idx is distinct within a worker
+  void* gbar;         // [n x ld] T mean table gradient (1 / m_i) sum_j tab[j] row_j, updated in place
+  int32_t init;
+};
+// per element-type pair (saga_f32.hip / saga_f64.hip / saga_x32.hip); cpl = 16-byte DATA chunks per lane
+hipError_t launch_saga_f32(int problem, int cpl, bool met, const SagaArgs& a, int n_workers, hipStream_t s);
+hipError_t launch_saga_f64(int problem, int cpl, bool met, const SagaArgs& a, int n_workers, hipStream_t s);
+hipError_t launch_saga_x32(int problem, int cpl, bool met, const SagaArgs& a, int n_workers, hipStream_t s);
+
 // ---- local steps (k_round_local.inc): tau gradient steps per gossip round in one launch, one
 // workgroup per worker
 //   u = sum_j W_ij x_j - eta[0] g_i(x_i),   u <- u - eta[k] g_i(u)  (k = 1 .. tau - 1),   x_new_i = u

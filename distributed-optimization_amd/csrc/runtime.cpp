@@ -14,6 +14,7 @@
 //   G      [N x ld]     T   per-worker gradients (centralized trainer, multi-GPU phases)
 //   ys[2], gprev [N x ld] T   gradient tracking: tracker ping-pong, previous stochastic gradients
 //   xh[2]  [N x ld]     T   CHOCO-SGD: ping-pong of the public copies xhat
+//   sg_tab [rows], sg_gbar [N x ld] T   GT-SAGA: one coefficient per shard row, the workers' mean table gradients
 //   sp_*                    sparse contexts (dopt_load_shards_csr): no X; the shards' CSR row view and column view
 //
 // Launch schedule of one D-SGD round t (metrics every round):
@@ -157,6 +158,11 @@ struct dopt_ctx {
   void* ps_phi = nullptr;
   int pcur = 0;
   void* ps_zt = nullptr;
+  // GT-SAGA (dopt_run_gt_saga): the table of row coefficients, [rows] T, and its mean gradient per worker,
+  // [N x ld] T; allocated (zero) on first use, valid once the opening pass of a chain has run (sg_ready)
+  void* sg_tab = nullptr;
+  void* sg_gbar = nullptr;
+  bool sg_ready = false;
   // softmax regression (dopt_load_shards_softmax): classes of the context, 0 for the vector objectives.  The
   // state rows (xs, xbar, part, S) then hold sm_C blocks of ld elements, class-major; ld / nch stay the data row's
   int sm_C = 0;
@@ -522,6 +528,9 @@ int alloc_state(dopt_ctx* c) {
   dfree(c->ps_phi);  // ... and the push-sum weights of dopt_run_pushsum (ones again on first use)
   dfree(c->ps_zt);
   c->pcur = 0;
+  dfree(c->sg_tab);  // ... and the SAGA table of dopt_run_gt_saga
+  dfree(c->sg_gbar);
+  c->sg_ready = false;
   c->cur = 0;
   c->gcur = 0;
   c->xb = 0;
@@ -1422,7 +1431,7 @@ int dopt_destroy(dopt_ctx* c) {
   if (c->stream) (void)hipStreamSynchronize(c->stream);
   if (c->own_stream) (void)hipStreamSynchronize(c->own_stream);
   for (void** p : {&c->X, &c->y, &c->Xo, &c->yo, &c->xs[0], &c->xs[1], &c->xg[0], &c->xg[1], &c->G, &c->ys[0], &c->ys[1],
-                   &c->gprev, &c->xh[0], &c->xh[1], &c->ps_phi, &c->ps_zt, &c->xbar[0], &c->xbar[1], &c->cw, &c->staging, &c->sx, &c->wdiag, &c->coef})
+                   &c->gprev, &c->xh[0], &c->xh[1], &c->ps_phi, &c->ps_zt, &c->sg_tab, &c->sg_gbar, &c->xbar[0], &c->xbar[1], &c->cw, &c->staging, &c->sx, &c->wdiag, &c->coef})
     dfree(*p);
   dfree_t(c->off);
   dfree_t(c->offo);
@@ -2129,6 +2138,189 @@ int dopt_gt_get_state(dopt_ctx* c, double* y, double* g) {
   if (y && (rc = download_rows(c, c->dtype, c->ys[c->ycur], y, c->n, c->d, c->ld))) return rc;
   if (g && (rc = download_rows(c, c->dtype, c->gprev, g, c->n, c->d, c->ld))) return rc;
   return DOPT_OK;
+}
+
+// ---------------------------------------------------------------------------- GT-SAGA
+namespace {
+
+// State of dopt_run_gt_saga beside the tracker's: table and mean table gradient, zero and not yet
+// valid (the first run opens the chain with the pass over every row).
+int ensure_saga(dopt_ctx* c) {
+  if (c->sg_tab && c->sg_gbar) return DOPT_OK;
+  const size_t tb = (size_t)std::max<int64_t>(1, c->rows) * c->esz;
+  const size_t st = (size_t)std::max<int64_t>(1, c->n) * c->ld * c->esz;
+  int rc;
+  if ((rc = dalloc(&c->sg_tab, tb))) return rc;
+  HIPOK(hipMemsetAsync(c->sg_tab, 0, tb, c->stream));
+  if ((rc = dalloc(&c->sg_gbar, st))) return rc;
+  HIPOK(hipMemsetAsync(c->sg_gbar, 0, st, c->stream));
+  c->sg_ready = false;
+  return DOPT_OK;
+}
+
+hipError_t launch_saga(dopt_ctx* c, bool met, const SagaArgs& g) {
+  if (c->dtype == DOPT_F32) return launch_saga_f32(c->problem, c->cpl, met, g, (int)c->n, c->stream);
+  if (c->xdtype == DOPT_F32) return launch_saga_x32(c->problem, c->cpl, met, g, (int)c->n, c->stream);
+  return launch_saga_f64(c->problem, c->cpl, met, g, (int)c->n, c->stream);
+}
+
+int check_saga(dopt_ctx* c) {
+  if (!c->have_data) return fail(DOPT_ERR_STATE, "no shards loaded");
+  if (c->split)
+    return fail(DOPT_ERR_UNSUPPORTED, "GT-SAGA: rows of %lld elements are column-blocked; the GT-SAGA round holds a "
+                "row per wave (at most %d 16-byte chunks per lane)", (long long)c->d,
+                max_chunks_per_lane(c->dtype, c->xdtype));
+  return DOPT_OK;
+}
+
+// The kernel scatters into the table by these indices: every one a worker uses must be a row of its shard.
+int check_saga_idx(dopt_ctx* c, const int32_t* idx, int64_t T, int64_t batch) {
+  for (int64_t h = 0; h < T; ++h)
+    for (int64_t i = 0; i < c->n; ++i) {
+      const int64_t m = c->off_h[(size_t)i + 1] - c->off_h[(size_t)i];
+      const int32_t* p = idx + (h * c->n + i) * batch;
+      for (int64_t k = 0, nb = std::min(batch, m); k < nb; ++k)
+        if (p[k] < 0 || p[k] >= m)
+          return fail(DOPT_ERR_INVALID, "idx: round %lld, worker %lld, entry %lld is %d, outside its shard of %lld rows",
+                      (long long)h, (long long)i, (long long)k, (int)p[k], (long long)m);
+    }
+  return DOPT_OK;
+}
+
+// T rounds of GT-SAGA on run_gt's schedule with k_round_saga in k_round_gt's place: the launch, then
+// the column sums of the new iterates with the history row of the previous round folded in; the
+// objective with host minibatches (or a separate objective dataset) takes the metrics-only pass
+// after every round, and the row of the last iterates one more launch without the step.  A chain's
+// first call opens with the kernel's pass over every row (table and mean table gradient at the
+// current iterates); later calls go straight to the rounds, so a run split into several calls
+// computes the bits of one call.
+int run_gt_saga(dopt_ctx* c, int64_t t0, int64_t T, double eta0, int64_t batch, const int32_t* idx, double lam_grad,
+                double lam_obj, double f_opt, uint32_t flags, double* obj_out, double* cons_out, double* time_out) {
+  CHECK_ARG(c, "ctx is NULL");
+  int rc;
+  if ((rc = check_saga(c))) return rc;
+  if (!c->have_topo) return fail(DOPT_ERR_STATE, "no topology set");
+  if (c->mean_mix)
+    return fail(DOPT_ERR_UNSUPPORTED, "GT-SAGA: mean mixing (dopt_set_mixing_mean) is not supported; give the "
+                "complete graph as CSR (dopt_set_topology)");
+  if (c->n_halo > 0 || c->n_send > 0 || c->sptr)
+    return fail(DOPT_ERR_UNSUPPORTED, "GT-SAGA: contexts with a halo plan (multi-GPU slices) are not supported");
+  if (!idx && batch < c->max_m && c->sampler == DOPT_SAMPLE_DEVICE)
+    return fail(DOPT_ERR_UNSUPPORTED, "GT-SAGA: the device sampler is not supported; pass idx");
+  if ((rc = check_run(c, T, batch, idx, true))) return rc;
+  if (idx && (rc = check_saga_idx(c, idx, T, batch))) return rc;
+  if ((rc = set_device(c))) return rc;
+  if ((rc = rs_end(c))) return rc;
+  c->carry_pending = false;
+  c->send_fresh = false;
+  if (T == 0) return DOPT_OK;
+  if ((rc = ensure_hist(c, T + 1))) return rc;
+  if ((rc = ensure_gt(c))) return rc;
+  if ((rc = ensure_saga(c))) return rc;
+  const bool want_obj = flags & DOPT_RUN_OBJECTIVE, want_cons = flags & DOPT_RUN_CONSENSUS;
+  const bool const_step = flags & DOPT_RUN_CONST_STEP;
+  const bool metrics = want_obj || want_cons;
+  const bool fuse_loss = want_obj && !idx && !c->obj_sep;  // the pass walks every objective row
+  const bool pass_loss = want_obj && !fuse_loss;
+  const int64_t CH = idx ? idx_chunk_rounds(c, T, batch) : 1;
+  int& xb = c->xb;
+  if ((rc = colsum_current(c))) return rc;  // xbar of the starting iterates
+  HIPOK(launch_stamp(c->stamps, c->stream));
+
+  auto saga_args = [&](bool step, bool met) {
+    SagaArgs g;
+    memset(&g, 0, sizeof(g));
+    g.r = base_args(c);
+    g.r.x_old = c->xs[c->cur];
+    g.r.x_new = c->xs[c->cur ^ 1];
+    g.r.xbar = c->xbar[xb];
+    g.r.lam = lam_grad;
+    g.r.b = batch;
+    g.r.flags |= (step ? F_STEP : 0) | (met && want_cons ? F_CONS : 0) | (met && fuse_loss ? F_LOSS : 0);
+    g.y_old = c->ys[c->ycur];
+    g.y_new = c->ys[c->ycur ^ 1];
+    g.g_prev = c->gprev;
+    g.tab = c->sg_tab;
+    g.gbar = c->sg_gbar;
+    if (g.r.flags & F_LOSS) c->loss_groups = c->n;  // per-worker loss slabs
+    return g;
+  };
+  // history row `row` = the slabs of the current launch (and, pass_loss, of the last metrics pass) at xbar[xb]
+  auto fold_args = [&](int64_t row) {
+    double* hr = c->hraw + 3 * row;
+    return FoldArgs{want_cons ? c->slab_cons : nullptr, c->n, want_obj ? c->slab_loss : nullptr, c->loss_groups,
+                    want_obj ? c->xbar[xb] : nullptr, hr, hr + 1, hr + 2};
+  };
+
+  if (!c->sg_ready) {  // the chain opens: tab = coef at the current iterates, gbar = its mean gradient
+    SagaArgs g = saga_args(false, false);
+    g.init = 1;
+    if (c->prof && (rc = prof_event(c, false))) return rc;
+    HIPOK(launch_saga(c, false, g));
+    if (c->prof && (rc = prof_event(c, true))) return rc;
+    c->sg_ready = true;
+  }
+  for (int64_t h = 0; h < T; ++h) {
+    const int64_t t = t0 + h;
+    if (idx && h % CH == 0) {
+      if ((rc = upload_idx_chunk(c, idx, h, std::min(CH, T - h), batch))) return rc;
+    }
+    const bool met = metrics && h > 0;
+    SagaArgs g = saga_args(true, met);
+    g.r.idx = idx ? c->idx + (h % CH) * c->n * batch : nullptr;
+    g.r.eta = const_step ? eta0 : eta0 / sqrt((double)(t + 1));
+    if (c->prof && (rc = prof_event(c, false))) return rc;
+    HIPOK(launch_saga(c, metrics, g));
+    if (c->prof && (rc = prof_event(c, true))) return rc;
+    // xbar of the new iterates and the stamp of the round's end; history[h - 1] rides the launch
+    const FoldArgs fold = fold_args(met ? h - 1 : 0);
+    HIPOK(launch_colsum(c->dtype, c->xs[c->cur ^ 1], c->n, c->ld, (int32_t)c->nchs, kRowsPerGroup, c->part,
+                        c->stamps + h + 1, n_div(c), c->xbar[xb ^ 1], nullptr, 0.0, 0, c->stream, c->S,
+                        met ? &fold : nullptr));
+    if (pass_loss && (rc = metrics_pass(c, c->xs[c->cur ^ 1], c->xbar[xb ^ 1], false, false, true))) return rc;
+    c->cur ^= 1;
+    c->ycur ^= 1;
+    xb ^= 1;
+  }
+  if (metrics) {  // the row of the last iterates; the column sums land in the spare xbar
+    const SagaArgs g = saga_args(false, true);
+    if (want_cons || fuse_loss) HIPOK(launch_saga(c, true, g));
+    const FoldArgs fold = fold_args(T - 1);
+    HIPOK(launch_colsum(c->dtype, c->xs[c->cur], c->n, c->ld, (int32_t)c->nchs, kRowsPerGroup, c->part, nullptr,
+                        n_div(c), c->xbar[xb ^ 1], nullptr, 0.0, 0, c->stream, c->S, &fold));
+  }
+  return finish_run(c, T, T, lam_obj, f_opt, want_obj ? obj_out : nullptr, want_cons ? cons_out : nullptr,
+                    time_out);
+}
+
+}  // namespace
+
+int dopt_run_gt_saga(dopt_ctx* c, int64_t t0, int64_t T, double eta0, int64_t batch, const int32_t* idx,
+                     double lam_grad, double lam_obj, double f_opt, uint32_t flags, double* obj_out, double* cons_out,
+                     double* time_out) {
+  if (c && (c->sm_C || c->sparse)) return no_dense(c, __func__);
+  return run_gt_saga(c, t0, T, eta0, batch, idx, lam_grad, lam_obj, f_opt, flags, obj_out, cons_out, time_out);
+}
+
+int dopt_saga_get_state(dopt_ctx* c, double* tab, double* gbar) {
+  if (c && (c->sm_C || c->sparse)) return no_dense(c, __func__);
+  CHECK_ARG(c, "ctx is NULL");
+  int rc;
+  if ((rc = check_saga(c))) return rc;
+  if ((rc = set_device(c))) return rc;
+  if ((rc = ensure_saga(c))) return rc;
+  if (tab && (rc = download_rows(c, c->dtype, c->sg_tab, tab, 1, c->rows, c->rows))) return rc;
+  if (gbar && (rc = download_rows(c, c->dtype, c->sg_gbar, gbar, c->n, c->d, c->ld))) return rc;
+  return DOPT_OK;
+}
+
+int dopt_saga_reset(dopt_ctx* c) {
+  if (c && (c->sm_C || c->sparse)) return no_dense(c, __func__);
+  CHECK_ARG(c, "ctx is NULL");
+  int rc;
+  if ((rc = check_saga(c))) return rc;
+  c->sg_ready = false;  // the next run opens a chain; table and mean gradient are rewritten there
+  return dopt_gt_set_state(c, nullptr, nullptr);
 }
 
 // ---------------------------------------------------------------------------- local steps

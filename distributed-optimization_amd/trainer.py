@@ -45,7 +45,18 @@ Config keys beyond the reference's (all optional):
              model is mean_i z_i, and total_floats_transmitted grows per round by
              sum(out_degrees) * (n_features + 1): u and phi travel on every directed edge.  Single
              process, host sampling, local_steps = 1, dense 'logistic' / 'quadratic' workers, no
+             checkpoints) or
+             'gt_saga' (GT-SAGA, variance-reduced gradient tracking: gradient_tracking's round with
+             the minibatch gradient replaced by the SAGA estimate
+             (1 / nb) sum_{j in B} (c_j(x_i) - tab_i[j]) row_j + gbar_i + lam x_i over a table of
+             one scalar per shard row and its mean gradient gbar_i, both updated in the round; the
+             run opens with a pass over every row that fills the table at the starting iterates.
+             One fused launch per round; total_floats_transmitted as gradient_tracking.  Single
+             process, host sampling, local_steps = 1, dense 'logistic' / 'quadratic' workers, no
              checkpoints)
+  step_rule  algorithm='gt_saga' only: 'decay' (default, eta_t = eta0 / sqrt(t + 1)) or 'constant'
+             (eta_t = eta0, the rule under which GT-SAGA converges linearly to the optimum);
+             ValueError for any other value, and for 'constant' with any other algorithm
   compression_k  algorithm='choco', required: entries sent per worker and round, an int in
              [1, n_features]
   choco_gamma    algorithm='choco', required: the consensus step size, a float in (0, 1]
@@ -77,6 +88,7 @@ contiguous slice of workers onto its own GPU; the rounds run through
 distributed.DistributedDSGD / DistributedCentralized (halo send/recv and
 all-reduces over RCCL) and every rank ends with the same history and iterates.
 """
+import functools
 import os
 import time
 from contextlib import closing
@@ -723,6 +735,11 @@ class DecentralizedTrainer:
         self.config = config
         self.adj = None
         self.degrees = None
+        step_rule = config.get("step_rule", "decay")
+        if step_rule not in ("decay", "constant"):
+            raise ValueError(f"step_rule {step_rule!r}: 'decay' or 'constant'")
+        if step_rule == "constant" and config.get("algorithm", "dsgd") != "gt_saga":
+            raise ValueError(f"step_rule='constant' runs algorithm='gt_saga', not {config.get('algorithm', 'dsgd')!r}")
         self.W = self._create_mixing_matrix()
         print(f"\n--- Running Decentralized SGD ({self.topology} - {self.config['problem_type']}) ---")
         self.history = {"objective": [], "consensus_error": [], "time": []}
@@ -845,11 +862,14 @@ class DecentralizedTrainer:
 
     def _run_gradient_tracking(self, algorithm, T, X_full, y_full, f_opt, lam_grad, reg_param, start_time):
         """config 'algorithm' = 'gradient_tracking': the rounds of Engine.run_gt in D-SGD's chunk loop,
-        from y = g = 0.  Every unsupported combination is refused before any device call."""
+        from y = g = 0; 'gt_saga': the same loop over Engine.run_gt_saga, a fresh chain (the first chunk
+        opens with the table pass).  Every unsupported combination is refused before any device call."""
         cfg = self.config
-        if algorithm != "gradient_tracking":
+        if algorithm not in ("gradient_tracking", "gt_saga"):
             raise ValueError(f"unknown algorithm {algorithm!r}: 'dsgd', 'gradient_tracking' or 'choco' -- or 'push_sum', "
-                             "the one that runs directed graphs")
+                             "the one that runs directed graphs, or 'gt_saga', gradient tracking with variance "
+                             "reduction")
+        saga = algorithm == "gt_saga"
         if _dist_info(cfg) is not None:
             raise NotImplementedError("gradient tracking runs in a single process (no multi-rank job)")
         if self._mean_mixing() and self._topo.uniform_offdiag() is not None:
@@ -865,15 +885,20 @@ class DecentralizedTrainer:
         t = self._topo
         eng.set_topology(t.row_ptr, t.col, t.w)
         eng.set_models(np.stack([np.asarray(w.x, dtype=np.float64) for w in self.workers]))
-        eng.gt_set_state(None, None)
+        if saga:
+            eng.saga_reset()
+            run = functools.partial(eng.run_gt_saga, const_step=cfg.get("step_rule", "decay") == "constant")
+        else:
+            eng.gt_set_state(None, None)
+            run = eng.run_gt
         iteration_transmission = 2 * np.sum(self.degrees) * self.n_features  # x and y both travel
         eta0 = cfg["learning_rate_eta0"]
         loop_start = time.perf_counter()
         with closing(_index_chunks(self.workers, T, cfg)) as chunks:
             for t0, n, b, idx, _ in chunks:
                 t_host = time.time() - start_time
-                obj, cons, tim = eng.run_gt(n, eta0, b, lam_grad, reg_param, f_opt, idx=idx, t0=t0,
-                                            objective=want_obj, consensus=True, want_time=True)
+                obj, cons, tim = run(n, eta0, b, lam_grad, reg_param, f_opt, idx=idx, t0=t0,
+                                     objective=want_obj, consensus=True, want_time=True)
                 self.history["consensus_error"].extend(list(cons))
                 if want_obj:
                     self.history["objective"].extend(list(obj))

@@ -62,7 +62,8 @@ extern "C" {
  *      dopt_run_softmax, dopt_softmax_set_models, dopt_softmax_get_models; sparse (CSR) shards --
  *      dopt_load_shards_csr, dopt_run_sparse; local steps (periodic gossip) -- dopt_run_local,
  *      DOPT_MAX_LOCAL_STEPS; push-sum (directed graphs) -- dopt_run_pushsum, dopt_pushsum_set_state,
- *      dopt_pushsum_get_state. */
+ *      dopt_pushsum_get_state; GT-SAGA (variance-reduced gradient tracking) -- dopt_run_gt_saga,
+ *      dopt_saga_get_state, dopt_saga_reset, DOPT_RUN_CONST_STEP. */
 #define DOPT_ABI_VERSION 9
 
 typedef struct dopt_ctx dopt_ctx;
@@ -91,6 +92,7 @@ typedef struct dopt_comm dopt_comm; /* an RCCL communicator the engine drives it
 /* run flags */
 #define DOPT_RUN_OBJECTIVE 1u /* record history['objective'] (trainer.py:188-191: X_full given) */
 #define DOPT_RUN_CONSENSUS 2u /* record history['consensus_error'] (trainer.py:182-186) */
+#define DOPT_RUN_CONST_STEP 4u /* dopt_run_gt_saga only: eta_t = eta0 in every round (no other run reads it) */
 
 int dopt_abi_version(void);
 const char *dopt_last_error(void);
@@ -258,6 +260,40 @@ int dopt_run_dsgd_pipelined(dopt_ctx *ctx, int64_t t0, int64_t T, double eta0, i
 int dopt_run_gt(dopt_ctx *ctx, int64_t t0, int64_t T, double eta0, int64_t batch,
                 const int32_t *idx, double lam_grad, double lam_obj, double f_opt,
                 uint32_t flags, double *obj_out, double *cons_out, double *time_out);
+
+/* T rounds of GT-SAGA (Xin, Khan, Kar 2020: gradient tracking along the SAGA estimate), rounds
+ * t0..t0+T-1 -- the reference has no such trainer.  The losses are generalised linear, the gradient
+ * of shard row j is c_j row_j with the scalar c_j = coef(x . row_j, y_j) (logistic: -y sigmoid(-y z),
+ * quadratic: z - y), so the SAGA table is one scalar per shard row.  Worker i with m_i rows, table
+ * tab_i, its mean gradient gbar_i = (1 / m_i) sum_j tab_i[j] row_j, batch B of nb = min(batch, m_i)
+ * DISTINCT local rows (the caller's contract, as the host samplers draw them; out-of-shard entries are
+ * DOPT_ERR_INVALID):
+ *   c_new_j = coef(x_i . row_j, y_j)                      j in B
+ *   s       = sum_{j in B} (c_new_j - tab_i[j]) row_j
+ *   g_new_i = s / nb + gbar_i + lam_grad x_i              (0, and nothing updated, for an empty shard)
+ *   gbar_i <- gbar_i + s / m_i;  tab_i[j] <- c_new_j      j in B
+ *   y_i <- sum_j W_ij y_j + g_new_i - g_i;  x_i <- sum_j W_ij x_j - eta_t y_i (the NEW y_i);  g_i <- g_new_i
+ * eta_t = eta0 / sqrt(t + 1), or eta0 with DOPT_RUN_CONST_STEP in flags.  y and g are the tracker
+ * state of dopt_run_gt (dopt_gt_set_state / dopt_gt_get_state).  The first call of a chain -- after
+ * loading or generating shards, or after dopt_saga_reset -- opens with a pass over every row at the
+ * current iterates, tab_i[j] = coef(x_i . row_j, y_j), gbar_i its mean gradient (no step, no
+ * regulariser); with full-shard batches the rounds are then dopt_run_gt's up to rounding.  One fused
+ * launch per round; arguments, outputs and history as dopt_run_gt.  A run split into several calls
+ * gives the bits of one call; dopt_set_models leaves the state alone.  The table is kept in the
+ * compute dtype.  DOPT_ERR_UNSUPPORTED: column-blocked contexts, mean mixing, a halo plan, the device
+ * sampler, softmax and sparse contexts. */
+int dopt_run_gt_saga(dopt_ctx *ctx, int64_t t0, int64_t T, double eta0, int64_t batch,
+                     const int32_t *idx, double lam_grad, double lam_obj, double f_opt,
+                     uint32_t flags, double *obj_out, double *cons_out, double *time_out);
+
+/* SAGA state of dopt_run_gt_saga as float64: tab = the table, one entry per shard row in shard order
+ * ([rows]); gbar = the mean table gradients, N x d row-major.  A NULL argument is skipped; both are
+ * zero before a chain's first run. */
+int dopt_saga_get_state(dopt_ctx *ctx, double *tab, double *gbar);
+
+/* Ends the GT-SAGA chain: the next dopt_run_gt_saga opens with the pass over every row, and the
+ * trackers y and g are zeroed (dopt_gt_set_state(ctx, NULL, NULL)). */
+int dopt_saga_reset(dopt_ctx *ctx);
 
 /* T communication rounds of D-SGD with local steps (Local SGD / periodic decentralized SGD), rounds
  * t0..t0+T-1 -- the reference has no such trainer: every worker takes local_steps gradient steps on
